@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/sec of the per-frame SD1.5 LCM denoising path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 A "step" is one frame through the whole hot path (BASELINE.json config 2, reference-faithful: u8 512x512
 frame resident in HBM -> Sobel/ControlNet conditioning -> TAESD encode -> 4 x (ControlNet + UNet + LCM step)
@@ -9,8 +9,16 @@ frame resident in HBM -> Sobel/ControlNet conditioning -> TAESD encode -> 4 x (C
 takes `--batch` of them per hipGraph replay (stacked along the GEMM M dimension: one pass over the 2.45 GB of weights
 serves all of them; every frame keeps its own GroupNorm statistics / attention / Sobel maximum) and keeps `--slots`
 launches in flight, one per launch lane (a lane = one of the process's four launch streams: four hardware queues on four
-command-processor pipes); K frames = ceil(K / batch) launches.  `--batch 1 --slots 1` is one frame at a time; the
-single-frame latency (`p50_latency_ms`) is always measured that way.
+command-processor pipes); K frames = K // batch launches, and when K is not a multiple of the batch one more launch of
+the remaining K mod batch frames, on an engine prepared for that many.  `--batch 1 --slots 1` is one frame at a time;
+the single-frame latency (`p50_latency_ms`) is always measured that way.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = ms per frame).
+`--full` adds everything else the line used to carry, each a run of its own after the timed steps: `value_long`, the
+end-to-end and latency legs, the other frames-per-launch operating points, the graph without ControlNet, the roofline pass,
+the sessions and API legs and the CPU baseline with its parity stamp (`--no-extras`, `--no-api`, `--no-cpu-baseline`
+thin that out).  `--dump-outputs DIR` writes what the last timed launch computed -- its u8 output frames, the arrays a
+caller of the engine receives -- to DIR/frames.npy as float32 [frames, H, W, 3] (rank 0's, with several GPUs).
 
 N GPUs: one process per GPU.  `--gpus N` without WORLD_SIZE in the environment makes THIS process a launcher that never
 touches the GPU: it starts N fresh children (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, one rank per
@@ -51,14 +59,19 @@ def parse_args(argv=None):
                     "lane also runs its ControlNet encoder on a side stream)")
     ap.add_argument("--batch", type=int, default=5, help="frames per launch (stacked along the GEMM M dimension); "
                     "--batch 1 --slots 3 is the one-frame-per-launch configuration of the first bench lines")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api", action="store_true", help="skip the leg through VideoSDPipeline.remote(...).infer.remote")
-    ap.add_argument("--no-extras", action="store_true", help="headline, latency and roofline only")
+    ap.add_argument("--full", action="store_true", help="after the headline, every other leg of the line (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed launch's output frames to DIR/frames.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity stamp")
+    ap.add_argument("--no-api", action="store_true", help="with --full: skip the leg through VideoSDPipeline.remote(...).infer.remote")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline, latency and roofline only")
     ap.add_argument("--retune", action="store_true", help="ignore profiles/tuning_mi355x.json and time all kernel configs again")
     ap.add_argument("--save-tuning", action="store_true", help="write the tuning table back to profiles/tuning_mi355x.json")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: walk the launch / rendezvous / broadcast / timing "
                     "protocol with a sleep as the step (CPU test of the multi-rank plumbing; the line says dry_run)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launcher (no GPU here)
@@ -182,6 +195,19 @@ def cpu_baseline(weights, text, frame, budget_s=20.0):
            "config1_s_per_frame": {"median": round(statistics.median(t1), 3), "min": round(min(t1), 3), "max": round(max(t1), 3), "frames": len(t1)},
            "config2_s_per_frame": {"min": round(min(times), 3), "max": round(max(times), 3), "frames": len(times)}}
     return rec, np.asarray(ref)
+
+
+def dump_outputs(out_dir, e):
+    """`--dump-outputs`: the u8 frames engine `e`'s last launch wrote (what `collect_u8` hands a caller) as float32
+    [frames, H, W, 3] in out_dir/frames.npy; the file stays under 64 MB (21 frames: a larger --batch keeps its last 21).  The
+    inputs are seeded (weights, prompt, frames, noise), so two builds run with the same arguments can be compared frame for frame."""
+    import numpy as np
+
+    e.ops.synchronize()
+    frames = e.out_u8.cpu().numpy().reshape(-1, H, W, 3)
+    frames = frames[-((64 << 20) // (frames[0].size * 4)):].astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frames.npy"), frames)
 
 
 def image_parity(got, ref):
@@ -341,7 +367,7 @@ def run_rank(args):
     eng, ops, weights = build_engine(local)
     # the four launch streams must sit on four different command-processor pipes: four frame-like kernel chains at once
     # against one alone (~1.0; >= 2 would mean two lanes take turns -- the "lottery" of rounds 1-3)
-    pipes_check = ops.pool_check()
+    pipes_check = ops.pool_check() if args.full else None
     tuning = os.path.join(ROOT, "profiles", "tuning_mi355x.json")
     if not args.retune:
         ops.load_tuning(tuning)  # per-shape (tile, split-K, pipeline) choices found by HipOps.tune_conv on an MI355X
@@ -375,11 +401,12 @@ def run_rank(args):
     plan = eng.prepare(H, W, LCM_STEPS, STRENGTH, controlnet_scale=1.0, use_controlnet=True, batch=B)
     launches_B = {"two_stream_form": eng.launches_by_kind()[0], "one_stream_form": eng.launches_by_kind(serial=True)[0]}
     prepare_ms = (time.perf_counter() - t_prep) * 1e3
-    # a slider step (strength / controlnet_scale): device constants only, same captured graph
-    t_upd = time.perf_counter()
-    eng.update_options(0.62, 1.05)
-    eng.update_options(STRENGTH, 1.0)
-    update_options_ms = (time.perf_counter() - t_upd) * 1e3 / 2
+    if args.full:
+        # a slider step (strength / controlnet_scale): device constants only, same captured graph
+        t_upd = time.perf_counter()
+        eng.update_options(0.62, 1.05)
+        eng.update_options(STRENGTH, 1.0)
+        update_options_ms = (time.perf_counter() - t_upd) * 1e3 / 2
     # frames are independent (the reference resets its RNG per frame): keep `slots` of them in flight per GPU,
     # each with its own buffers, streams and hipGraph, sharing the weight replica
     engines = [eng]
@@ -389,6 +416,15 @@ def run_rank(args):
         sl.tune_for_lanes = eng.tune_for_lanes
         sl.prepare(H, W, LCM_STEPS, STRENGTH, controlnet_scale=1.0, use_controlnet=True, batch=B)
         engines.append(sl)
+    # exactly K timed frames: K // B launches of B frames, then the K mod B frames left as one launch of an engine prepared for
+    # that many, on the lane the launch sequence has reached (it takes its turn behind that lane's previous launch)
+    n_full, rem = divmod(args.steps, B)
+    tail = None
+    if rem:
+        tail = eng.make_slot(lane=engines[n_full % len(engines)].ops.lane)
+        tail.overlap_launch = eng.overlap_launch
+        tail.tune_for_lanes = args.slots >= 3 and rem > 1 and not os.environ.get("VSD_NO_LANE_TUNING")
+        tail.prepare(H, W, LCM_STEPS, STRENGTH, controlnet_scale=1.0, use_controlnet=True, batch=rem)
 
     # this rank's shard of the synthetic stream, resident in HBM before the timed region
     nres = max(12, B)
@@ -408,16 +444,20 @@ def run_rank(args):
         for e in (pool or engines):
             e.ops.synchronize()
 
-    n_launch = -(-args.steps // B)  # K frames = ceil(K / B) launches (a ragged last launch still does B frames of work)
+    n_launch = n_full + (tail is not None)
     for i in range(max(-(-args.warmup // B), len(engines))):  # W warm-up frames, and at least one replay of every slot's graph
         one_frame(i)
+    if tail is not None:
+        one_frame(n_full, [tail])
     sync_all()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(n_launch):
+    for i in range(n_full):
         one_frame(i)
+    if tail is not None:
+        one_frame(n_full, [tail])
     sync_all()
     torch.cuda.synchronize()
     if dist is not None:
@@ -428,6 +468,43 @@ def run_rank(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     fps = world * args.steps / dt
+    last = tail if tail is not None else engines[(n_full - 1) % len(engines)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    if args.save_tuning and not args.full:
+        ops.save_tuning(tuning)
+
+    out = {
+        "metric": METRIC,
+        "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f16 (fp32 accumulate)", "data": "synthetic", "ranks_seen": ranks_seen,
+        "config": {"workload": f"{B} frames per launch x {len(engines)} launch lanes in flight (a stream's independent frames coalesced along GEMM M; "
+                               "the batch=1-per-launch figures of a --full run are fps_one_frame_per_launch and p50_latency_ms) of "
+                               "SD1.5 512x512 LCM 4-step img2img, every frame denoised independently, ControlNet-canny + TAESD "
+                               "(BASELINE configs[1], reference-faithful: the reference always runs ControlNet)",
+                   "frames_per_rank": args.steps, "sharding": f"round-robin frames over {world} GPU(s)",
+                   "frames_per_launch": B, "launches_in_flight_per_gpu": len(engines),
+                   "timed_launches": {"of_%d_frames" % B: n_full, "of_%d_frames" % rem: 1} if rem else {"of_%d_frames" % B: n_full},
+                   "timesteps": plan["timesteps"],
+                   # kernels one replay issues (Engine.launches_by_kind: reducers and second GroupNorm kernels counted, a pair / group of
+                   # calls sharing a grid once): the timed program runs the one-stream form (lanes >= 3), a lone frame the two-stream form
+                   "kernel_launches_per_graph_replay": launches_B["one_stream_form" if len(engines) >= 3 else "two_stream_form"],
+                   "kernel_launches_by_form": {"frames_per_launch_%d" % B: launches_B},
+                   "recorded_ops": {"frames_per_launch_%d" % B: plan["n_ops"]}},
+        "launch_streams": {"lanes": "lane l = launch stream l mod 4 (CU-masked: own hardware queue), side branch on (l + 2) mod 4",
+                           "graphs_per_launch": plan.get("graphs"), "event_edges_per_launch": plan.get("edges")},
+        "prepare_ms": round(prepare_ms, 1),
+        "frame_roofline": {"algorithmic_tflop_per_frame": 4.623, "mfma_frac": round(4.623 * fps / world / MFMA_PEAK_TFLOPS, 4)},
+    }
+    if not args.full:  # a plain run: the headline is all
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # the same plan timed for >= 2 s (the driver's --steps 20 is 0.17 s: 4 launches): a cross-check inside the line itself
     n_long = max(n_launch, int(2.2 / max(dt / n_launch, 1e-4)) + 1)
     torch.cuda.synchronize()
@@ -642,26 +719,13 @@ def run_rank(args):
                 "families_ms_per_pass": {k: round(v["ms"], 3) for k, v in st.items()},
                 "in_situ": in_situ}
 
-    out = {
-        "metric": METRIC,
-        "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+    # (p50_latency_ms is a lone frame in the two-stream form; 1 x 4 runs the one-stream form: kernel_launches_by_form)
+    out["config"]["kernel_launches_per_single_frame_graph"] = launches_1["two_stream_form"]
+    out["config"]["kernel_launches_by_form"]["one_frame"] = launches_1
+    out["config"]["recorded_ops"]["one_frame"] = plan1["n_ops"]
+    out["launch_streams"]["four_chains_vs_one"] = round(pipes_check, 3)
+    out.update({
         "value_long": round(fps_long, 3), "value_long_seconds": round(dt_long, 2),
-        "vs_baseline": None, "dtype": "f16 (fp32 accumulate)", "data": "synthetic", "ranks_seen": ranks_seen,
-        "config": {"workload": f"{B} frames per launch x {len(engines)} launch lanes in flight (a stream's independent frames coalesced along GEMM M; "
-                               "the batch=1-per-launch figures of the same run are fps_one_frame_per_launch and p50_latency_ms) of "
-                               "SD1.5 512x512 LCM 4-step img2img, every frame denoised independently, ControlNet-canny + TAESD "
-                               "(BASELINE configs[1], reference-faithful: the reference always runs ControlNet)",
-                   "frames_per_rank": args.steps, "sharding": f"round-robin frames over {world} GPU(s)",
-                   "frames_per_launch": B, "launches_in_flight_per_gpu": len(engines),
-                   "timesteps": plan["timesteps"],
-                   # kernels one replay issues (Engine.launches_by_kind: reducers and second GroupNorm kernels counted, a pair / group of
-                   # calls sharing a grid once): the timed program runs the one-stream form (lanes >= 3), a lone frame the two-stream form
-                   "kernel_launches_per_graph_replay": launches_B["one_stream_form" if len(engines) >= 3 else "two_stream_form"],
-                   # (p50_latency_ms is a lone frame in the two-stream form; 1 x 4 runs the one-stream form: kernel_launches_by_form)
-                   "kernel_launches_per_single_frame_graph": launches_1["two_stream_form"],
-                   "kernel_launches_by_form": {"frames_per_launch_%d" % B: launches_B, "one_frame": launches_1},
-                   "recorded_ops": {"frames_per_launch_%d" % B: plan["n_ops"], "one_frame": plan1["n_ops"]}},
         "p50_latency_ms": round(p50, 3),
         "p50_latency_ms_under_load": round(statistics.median(lat_loaded), 3) if lat_loaded else None,
         "p50_latency_ms_under_load_one_frame_per_launch_x4": round(statistics.median(lat_loaded_1x4), 3) if lat_loaded_1x4 else None,
@@ -669,13 +733,9 @@ def run_rank(args):
         "fps_by_frames_per_launch_x_launches_in_flight": fps_by_b or None,
         "fps_end_to_end": round(fps_e2e, 3) if fps_e2e else None,
         "fps_without_controlnet": round(fps_nocn, 3),
-        "launch_streams": {"lanes": "lane l = launch stream l mod 4 (CU-masked: own hardware queue), side branch on (l + 2) mod 4",
-                           "four_chains_vs_one": round(pipes_check, 3),
-                           "graphs_per_launch": plan.get("graphs"), "event_edges_per_launch": plan.get("edges")},
-        "prepare_ms": round(prepare_ms, 1), "update_options_ms": round(update_options_ms, 2),
-        "frame_roofline": {"algorithmic_tflop_per_frame": 4.623, "mfma_frac": round(4.623 * fps / world / MFMA_PEAK_TFLOPS, 4)},
+        "update_options_ms": round(update_options_ms, 2),
         "roofline": roofline,
-    }
+    })
     if extras:
         try:
             out.update(sessions_leg(frames_host, local))

@@ -6,12 +6,14 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 TAG=${1:-r1}
 NB=${2:-5}
 mkdir -p gpurun_out
-# 1. the bench command under the kernel tracer
+# 1. the bench command under the kernel tracer, every leg of its line (--full); its line and kernel stats go to $OUT (default prof_out/)
+OUT=${OUT:-prof_out}
+mkdir -p "$OUT"
 rm -rf /tmp/prof_bench
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 bench.py --steps 30 --warmup 6 --no-cpu-baseline --no-api > gpurun_out/${TAG}_bench_under_rocprof.json 2>/tmp/err_bench.log
-python3 scripts/shorten_stats.py /tmp/prof_bench/*/*_kernel_stats.csv gpurun_out/${TAG}_bench_kernel_stats.csv
-tail -c 600 gpurun_out/${TAG}_bench_under_rocprof.json; echo
-head -8 gpurun_out/${TAG}_bench_kernel_stats.csv | cut -c1-160
+rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR/prof_bench" -- python3 bench.py --full --steps 30 --warmup 6 --no-cpu-baseline --no-api > "$OUT/${TAG}_bench_under_rocprof.json" 2>"$OUT/${TAG}_bench.err"
+python3 scripts/shorten_stats.py "$TMPDIR"/prof_bench/*/*_kernel_stats.csv "$OUT/${TAG}_bench_kernel_stats.csv"
+tail -c 600 "$OUT/${TAG}_bench_under_rocprof.json"; echo
+head -8 "$OUT/${TAG}_bench_kernel_stats.csv" | cut -c1-160
 # 2. per-layer tables
 for B in 1 $NB; do
   rm -rf /tmp/pf$B

@@ -16,6 +16,9 @@ class FakeOps:
     def __init__(self):
         self.device = torch.device("cpu")
         self.tile_override = {}
+        # HipOps.stream: where the engine records its staging events.  The engine stages through pinned host memory and times with
+        # events whenever a GPU is present (Engine._staging), so on a GPU machine the emulator needs a real stream to record them on.
+        self.stream = torch.cuda.current_stream() if torch.cuda.is_available() else None
 
     def empty(self, *shape, dtype=torch.float16):
         return torch.zeros(*shape, dtype=dtype)
@@ -64,6 +67,8 @@ class FakeOps:
 
     def download_into(self, dst_cpu, src):
         dst_cpu.view(src.shape).copy_(src)
+        if self.stream is not None:  # (as HipOps: then wait for the stream, so that the events recorded around the launch are complete)
+            self.stream.synchronize()
 
     @staticmethod
     def _nhwc(t, h, w, c, b=1):
