@@ -465,7 +465,9 @@ __device__ __forceinline__ void attention_body(const AttnParams& pp, const unsig
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) {
         float* b = mg + qb * (NPV * 16 + 2) * 64;
-        b[0] = m_run[qb];
+        // LAZY: a group that got no key tile (a single tile in all) still holds its initial offset 0, which is no maximum: with
+        // every logit of a row far below zero, max(m0, 0) = 0 would scale group 0's O and row sum to 0 and the output to NaN
+        b[0] = (LAZY && lazy_first) ? NEG_BIG : m_run[qb];
         b[64] = l_run[qb];
 #pragma unroll
         for (int i = 0; i < NPV; ++i)
