@@ -51,10 +51,10 @@ enum vsd_family {
   VSD_FAM_ATTENTION = 4, VSD_FAM_ELEMENTWISE = 5, VSD_FAM_COUNT = 6
 };
 
-/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*) and the size in
+/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
-#define VSD_VERSION 6
+#define VSD_VERSION 7
 int vsd_version(void);
 int vsd_conv_desc_size(void);
 
@@ -280,6 +280,34 @@ int vsd_postprocess_rgb(vsd_ctx* ctx, const void* img, int ld, int hw, void* rgb
 /* out = a + b * scale   (fp16, n elements, n % 8 == 0) */
 int vsd_axpy(vsd_ctx* ctx, const void* a, const void* b, float scale, int64_t n, void* out, void* stream);
 
+/* ---- centre crop + LANCZOS resize of a camera frame, bit for bit Pillow's (csrc/resample.hip) -------------------------------------
+ * Replaces the PIL `img.crop(box).resize((width, height), LANCZOS)` in front of every frame (videopipeline.py:92-107): the camera
+ * frame is uploaded as it is and cropped / resampled on the device into the engine's input frame.  Pillow's 8-bit resample is integer
+ * arithmetic on 22-bit fixed-point weight tables; the tables are computed on the HOST (double, the C library's sin, as Pillow does),
+ * the two passes (horizontal into an 8-bit intermediate, then vertical; a pass whose input length equals its output length is
+ * skipped) run on the device.  Every byte equals Pillow's.
+ * vsd_center_crop_box: host only.  The crop box of the reference for a src_w x src_h frame and a dst_w x dst_h target:
+ *   box = {left, top, right, bottom}, the float box rounded half to even per edge like Python's int(round(v)).
+ * A table serves one axis and one (in, out) pair of lengths (in = the BOX's side, out = the target's side), each 1..VSD_RESAMPLE_MAX_SIDE;
+ *   any ratio works (3840 x 2160 -> 512 x 512 or smaller included).  Layout, int32: xmin[out] | count[out] | k[out][ksize]: output i is
+ *   clamp((2^21 + sum_{t < count[i]} pixel[xmin[i] + t] * k[i][t]) >> 22, 0, 255).  vsd_resample_table_bytes: its size (0 = lengths
+ *   outside the limits).  vsd_resample_table_host: host only (works without a GPU); fills the three arrays (coeffs: out * ksize
+ *   int32, ksize = table_bytes / (4 * out) - 2) and returns ksize.  vsd_resample_table_upload: builds the table and puts it into
+ *   `table_dev` (>= table_bytes, 4-byte aligned, device memory); waits for `stream`.
+ * vsd_resample_rgb: src_u8 = packed RGB rows of src_row_bytes >= 3 * src_w bytes; box inside the source and not empty;
+ *   dst_u8 = packed [dst_h][dst_w][3] (the layout of the frame vsd_preprocess_rgb / vsd_sobel_control read).  table_x for
+ *   (box width -> dst_w), table_y for (box height -> dst_h); the table of a skipped pass may be NULL.  workspace: >=
+ *   vsd_resample_workspace_bytes(box height, dst_w) bytes when both passes run, else unused.  src, dst and workspace must not overlap.
+ *   Anything else is refused with VSD_ERR_ARG and a reason.  One launch per pass. */
+#define VSD_RESAMPLE_MAX_SIDE 16384
+int vsd_center_crop_box(int src_w, int src_h, int dst_w, int dst_h, int* box);
+int64_t vsd_resample_table_bytes(int in, int out);
+int vsd_resample_table_host(int in, int out, int32_t* xmin, int32_t* count, int32_t* coeffs);
+int vsd_resample_table_upload(vsd_ctx* ctx, int in, int out, void* table_dev, void* stream);
+int64_t vsd_resample_workspace_bytes(int box_h, int dst_w);
+int vsd_resample_rgb(vsd_ctx* ctx, const void* src_u8, int src_h, int src_w, int64_t src_row_bytes, const int* box, void* dst_u8,
+                     int dst_h, int dst_w, const void* table_x, const void* table_y, void* workspace, void* stream);
+
 /* ---- two independent operations as ONE grid per kernel ------------------------------------------------
  * The reference runs the ControlNet and then the UNet encoder of a denoising step -- the same topology with two weight sets on the
  * same latents (lcm_controlnet.py:539-577) -- as two sequences of cuDNN / cuBLAS launches.  Here the two walk in lock step:
@@ -313,6 +341,12 @@ int vsd_plan_info(vsd_ctx* ctx, vsd_plan* plan, int* dims);
 int vsd_plan_submit(vsd_ctx* ctx, vsd_plan* plan, const void* frame_u8_host, void* out_u8_host);
 int vsd_plan_wait(vsd_ctx* ctx, vsd_plan* plan);
 int vsd_plan_infer(vsd_ctx* ctx, vsd_plan* plan, const void* frame_u8_host, void* out_u8_host);
+/* The same for a CAMERA frame of any size (packed u8 RGB rows of src_row_bytes >= 3 * src_w bytes on the host; frames per launch > 1:
+ * that many frames of this one size, src_h * src_row_bytes bytes apart): crop box of vsd_center_crop_box, upload of the box alone,
+ * vsd_resample_rgb into the plan's input frame, graph launch, download -- what VideoSDPipeline.infer does with a PIL image, bit for bit.
+ * A new source size costs two tables, not a new plan.  Sizes: as for vsd_resample_rgb. */
+int vsd_plan_submit_frame(vsd_ctx* ctx, vsd_plan* plan, const void* src_u8_host, int src_h, int src_w, int64_t src_row_bytes, void* out_u8_host);
+int vsd_plan_infer_frame(vsd_ctx* ctx, vsd_plan* plan, const void* src_u8_host, int src_h, int src_w, int64_t src_row_bytes, void* out_u8_host);
 /* another prompt for a loaded plan: a file written by videosd_amd.plan.export_prompt (the prompt's constant block, same layout) */
 int vsd_plan_load_prompt(vsd_ctx* ctx, vsd_plan* plan, const char* path);
 void vsd_plan_free(vsd_ctx* ctx, vsd_plan* plan);

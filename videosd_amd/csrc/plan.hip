@@ -39,6 +39,10 @@ struct vsd_plan {
   void* graph = nullptr;
   void *in = nullptr, *out = nullptr, *prompt = nullptr;
   size_t io_bytes = 0, prompt_bytes = 0;
+  // camera frames (vsd_plan_submit_frame): the uploaded crop boxes, the intermediate of the two passes and the tables of the last source size
+  void *raw = nullptr, *work = nullptr, *table_x = nullptr, *table_y = nullptr;
+  size_t raw_bytes = 0, work_bytes = 0;
+  int table_x_in = 0, table_y_in = 0;
 };
 
 namespace {
@@ -70,6 +74,8 @@ void plan_release(vsd_plan* p) {
   if (p->graph) (void)hipGraphExecDestroy((hipGraphExec_t)p->graph);
   if (p->stream && p->own_stream) (void)hipStreamDestroy(p->stream);
   for (void* r : p->regions)
+    if (r) (void)hipFree(r);
+  for (void* r : {p->raw, p->work, p->table_x, p->table_y})
     if (r) (void)hipFree(r);
   delete p;
 }
@@ -245,6 +251,70 @@ extern "C" int vsd_plan_wait(vsd_ctx* ctx, vsd_plan* plan) {
 
 extern "C" int vsd_plan_infer(vsd_ctx* ctx, vsd_plan* plan, const void* frame_u8_host, void* out_u8_host) {
   const int rc = vsd_plan_submit(ctx, plan, frame_u8_host, out_u8_host);
+  return rc != VSD_OK ? rc : vsd_plan_wait(ctx, plan);
+}
+
+// A camera frame of any size: crop box (vsd_center_crop_box), upload of the box alone, resample into the plan's input frame, then as
+// vsd_plan_submit.  The resample runs in front of the captured graph, not inside it: another source size is another pair of tables.
+extern "C" int vsd_plan_submit_frame(vsd_ctx* ctx, vsd_plan* plan, const void* src_u8_host, int src_h, int src_w, int64_t src_row_bytes, void* out_u8_host) {
+  if (!ctx || !plan || !src_u8_host || !out_u8_host) return VSD_ERR_ARG;
+  if (src_h < 1 || src_w < 1 || src_h > VSD_RESAMPLE_MAX_SIDE || src_w > VSD_RESAMPLE_MAX_SIDE || src_row_bytes < (int64_t)3 * src_w)
+    return vsd_fail(ctx, VSD_ERR_ARG, "plan_submit_frame: a %d x %d source with rows of %lld bytes (sides 1..%d, rows of at least 3 * width bytes)", src_w, src_h,
+                    (long long)src_row_bytes, VSD_RESAMPLE_MAX_SIDE);
+  int box[4];
+  if (vsd_center_crop_box(src_w, src_h, plan->W, plan->H, box) != VSD_OK) return vsd_fail(ctx, VSD_ERR_ARG, "plan_submit_frame: no crop box");
+  const int bw = box[2] - box[0], bh = box[3] - box[1];
+  if (box[0] < 0 || box[1] < 0 || bw < 1 || bh < 1 || box[2] > src_w || box[3] > src_h)
+    return vsd_fail(ctx, VSD_ERR_ARG, "plan_submit_frame: the crop box of a %d x %d source for %d x %d is empty", src_w, src_h, plan->W, plan->H);
+  const unsigned char* src = (const unsigned char*)src_u8_host + (size_t)box[1] * src_row_bytes + (size_t)box[0] * 3;
+  const size_t row = (size_t)bw * 3, one = row * bh, frame = (size_t)plan->H * plan->W * 3;
+  if (bw == plan->W && bh == plan->H) {  // already the target size: the box goes straight into the input frame
+    for (int b = 0; b < plan->batch; ++b)
+      VSD_HIP(ctx, hipMemcpy2DAsync((char*)plan->in + b * frame, row, src + (size_t)b * src_h * src_row_bytes, (size_t)src_row_bytes, row, (size_t)bh,
+                                    hipMemcpyHostToDevice, plan->stream));
+  } else {
+    auto grow = [&](void** p, size_t* have, size_t need) -> int {
+      if (*have >= need) return VSD_OK;
+      VSD_HIP(ctx, hipStreamSynchronize(plan->stream));  // (nothing in flight reads the old buffer)
+      if (*p) (void)hipFree(*p);
+      *p = nullptr;
+      *have = 0;
+      if (hipMalloc(p, need) != hipSuccess) return vsd_fail(ctx, VSD_ERR_NOMEM, "plan_submit_frame: out of device memory (%zu bytes)", need);
+      *have = need;
+      return VSD_OK;
+    };
+    auto table = [&](void** t, int* have_in, int in, int out) -> int {
+      if (in == out || *have_in == in) return VSD_OK;
+      VSD_HIP(ctx, hipStreamSynchronize(plan->stream));
+      if (*t) (void)hipFree(*t);
+      *t = nullptr;
+      *have_in = 0;
+      if (hipMalloc(t, (size_t)vsd_resample_table_bytes(in, out)) != hipSuccess) return vsd_fail(ctx, VSD_ERR_NOMEM, "plan_submit_frame: out of device memory (table)");
+      const int rc = vsd_resample_table_upload(ctx, in, out, *t, (void*)plan->stream);
+      if (rc == VSD_OK) *have_in = in;
+      return rc;
+    };
+    int rc = grow(&plan->raw, &plan->raw_bytes, one * plan->batch);
+    if (rc == VSD_OK) rc = grow(&plan->work, &plan->work_bytes, (size_t)vsd_resample_workspace_bytes(bh, plan->W));
+    if (rc == VSD_OK) rc = table(&plan->table_x, &plan->table_x_in, bw, plan->W);
+    if (rc == VSD_OK) rc = table(&plan->table_y, &plan->table_y_in, bh, plan->H);
+    if (rc != VSD_OK) return rc;
+    const int whole[4] = {0, 0, bw, bh};
+    for (int b = 0; b < plan->batch; ++b) {
+      VSD_HIP(ctx, hipMemcpy2DAsync((char*)plan->raw + b * one, row, src + (size_t)b * src_h * src_row_bytes, (size_t)src_row_bytes, row, (size_t)bh,
+                                    hipMemcpyHostToDevice, plan->stream));
+      rc = vsd_resample_rgb(ctx, (char*)plan->raw + b * one, bh, bw, (int64_t)row, whole, (char*)plan->in + b * frame, plan->H, plan->W, plan->table_x,
+                            plan->table_y, plan->work, (void*)plan->stream);
+      if (rc != VSD_OK) return rc;
+    }
+  }
+  VSD_HIP(ctx, hipGraphLaunch((hipGraphExec_t)plan->graph, plan->stream));
+  VSD_HIP(ctx, hipMemcpyAsync(out_u8_host, plan->out, plan->io_bytes, hipMemcpyDeviceToHost, plan->stream));
+  return VSD_OK;
+}
+
+extern "C" int vsd_plan_infer_frame(vsd_ctx* ctx, vsd_plan* plan, const void* src_u8_host, int src_h, int src_w, int64_t src_row_bytes, void* out_u8_host) {
+  const int rc = vsd_plan_submit_frame(ctx, plan, src_u8_host, src_h, src_w, src_row_bytes, out_u8_host);
   return rc != VSD_OK ? rc : vsd_plan_wait(ctx, plan);
 }
 

@@ -498,6 +498,7 @@ class Engine:
         e.graph_serial = None
         e.plan = None
         e._stage = None  # own pinned staging buffers and events (a copy of the parent's would be SHARED with it)
+        e._raw_stage = None
         e.pblock = None
         e._installed = None
         e._want = None
@@ -1525,6 +1526,58 @@ class Engine:
         self.launch(overlap)
         if e1 is not None:
             e1.record(self.ops.stream)
+
+    def _raw_staging(self, nbytes: int):
+        """Pinned host bytes and device bytes for the crop boxes of camera frames (`submit_raw_u8`); grown, never shrunk.  The lane's
+        previous launch has been collected (= its stream waited for) before the next submit, so nothing in flight reads the old ones."""
+        st = getattr(self, "_raw_stage", None)
+        if st is None or st[0].numel() < nbytes:
+            n = _ru(max(nbytes, 1 << 20), 1 << 20)
+            st = (torch.empty(n, dtype=torch.uint8, pin_memory=torch.cuda.is_available()), self.ops.empty(n, dtype=torch.uint8))
+            self._raw_stage = st
+        return st
+
+    def submit_raw_u8(self, frame, overlap: Optional[bool] = None):
+        """`submit_u8` for CAMERA frames: uint8 [h][w][3] of any size (prepared with batch B > 1: a list of B frames, possibly of
+        different sizes).  The reference's centre crop + LANCZOS resize (videopipeline.py:92-107) runs on the device: the crop box
+        alone is uploaded and resampled into `frame_u8` by an ordinary launch in front of the captured program, bit for bit what
+        PIL gives on the host.  A frame already of the plan's size goes straight into `frame_u8`."""
+        p = self.plan
+        H, W, B = p["H"], p["W"], p["batch"]
+        frames = [frame] if B == 1 and isinstance(frame, np.ndarray) else list(frame)
+        if len(frames) != B:
+            raise ValueError(f"this engine takes {B} frame(s) per launch, got {len(frames)}")
+        boxes, total = [], 0
+        for f in frames:
+            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
+                raise ValueError(f"frame must be uint8 [h][w][3], got {getattr(f, 'dtype', type(f))} {getattr(f, 'shape', '')}")
+            l, t, r, b = self.ops.center_crop_box(f.shape[1], f.shape[0], W, H)
+            if not (0 <= l < r <= f.shape[1] and 0 <= t < b <= f.shape[0]):
+                raise ValueError(f"the crop box of a {f.shape[1]} x {f.shape[0]} frame for {W} x {H} is empty")
+            boxes.append((l, t, r, b, total))
+            total += _ru((r - l) * (b - t) * 3, 256)
+        hraw, draw = self._raw_staging(total)
+        _, _hin, _hout, e0, e1 = self._staging()
+        for i, (f, (l, t, r, b, off)) in enumerate(zip(frames, boxes)):
+            bw, bh = r - l, b - t
+            n = bw * bh * 3
+            hraw.numpy()[off:off + n].reshape(bh, bw, 3)[...] = f[t:b, l:r]  # (only the crop box travels)
+            dst = self.frame_u8 if B == 1 else self.frame_u8[i]
+            if (bh, bw) == (H, W):
+                self.ops.upload(dst, hraw[off:off + n])
+            else:
+                self.ops.upload(draw[off:off + n], hraw[off:off + n])
+                self.ops.resample_rgb(draw[off:off + n], bh, bw, bw * 3, (0, 0, bw, bh), dst, H, W)
+        if e0 is not None:
+            e0.record(self.ops.stream)
+        self.launch(overlap)
+        if e1 is not None:
+            e1.record(self.ops.stream)
+
+    def infer_raw_u8(self, frame) -> np.ndarray:
+        """camera frame(s) of any size -> uint8 [H][W][3] ([B][H][W][3]): `infer_u8` of the centre-cropped, LANCZOS-resized frame(s)"""
+        self.submit_raw_u8(frame)
+        return self.collect_u8()
 
     def collect_u8(self) -> np.ndarray:
         """Wait for the frame(s) enqueued by the last `submit_u8` and bring them to the host (a fresh array)."""

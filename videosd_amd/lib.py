@@ -7,12 +7,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # VSD_LIB: another build of the same sources (development: the instrumented libvsd_tl.so of build.build_timeline)
 LIB_PATH = os.environ.get("VSD_LIB") or os.path.join(HERE, "libvsd.so")
 
-VERSION = 6  # include/vsd.h VSD_VERSION
+VERSION = 7  # include/vsd.h VSD_VERSION
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GEGLU, ACT_QUICKGELU, ACT_SOFTMAX, ACT_GELU = range(7)
 ACT_POST = 256
 SPLITK_MAX_TILES = 16384
 POOL_STREAMS = 4  # include/vsd.h VSD_POOL_STREAMS
 CONV_GROUP_MAX = 8  # include/vsd.h VSD_CONV_GROUP_MAX
+RESAMPLE_MAX_SIDE = 16384  # include/vsd.h VSD_RESAMPLE_MAX_SIDE
 TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128, TILE_256x128, TILE_256x64, TILE_256x256 = range(7)
 TILE_DIMS = {TILE_128x128: (128, 128), TILE_128x64: (128, 64), TILE_64x64: (64, 64), TILE_64x128: (64, 128),
              TILE_256x128: (256, 128), TILE_256x64: (256, 64), TILE_256x256: (256, 256)}
@@ -93,6 +94,13 @@ SIGNATURES = {
     "vsd_embed_tokens": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vsd_postprocess_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vsd_axpy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p]),
+    "vsd_center_crop_box": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
+    "vsd_resample_table_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "vsd_resample_table_host": (C.c_int, [C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3),
+    "vsd_resample_table_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vsd_resample_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "vsd_resample_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vsd_graph_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vsd_graph_end": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "vsd_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -114,6 +122,8 @@ SIGNATURES = {
     "vsd_plan_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vsd_plan_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vsd_plan_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vsd_plan_submit_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "vsd_plan_infer_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "vsd_plan_load_prompt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p]),
     "vsd_plan_free": (None, [C.c_void_p, C.c_void_p]),
     "vsd_pinned_alloc": (C.c_void_p, [C.c_void_p, C.c_size_t]),

@@ -922,6 +922,41 @@ class HipOps:
         self.ctx.call("vsd_attention", self._p(q), ldq, self._p(k), ldk, self._p(vt), ldvt, self._p(out), ldo, sq, sk,
                       heads, d, scale, int(causal), self.s)
 
+    RESAMPLE_TABLES = 16  # (in, out) weight tables kept per object: a camera that changes resolution costs a table, not more
+
+    def center_crop_box(self, src_w: int, src_h: int, dst_w: int, dst_h: int):
+        """the reference's crop box (videopipeline.py:92-107) with PIL's rounding: (left, top, right, bottom)"""
+        b = (C.c_int * 4)()
+        if self.ctx.lib.vsd_center_crop_box(int(src_w), int(src_h), int(dst_w), int(dst_h), b) != 0:  # (host only: no context)
+            raise ValueError(f"center_crop_box: {src_w} x {src_h} -> {dst_w} x {dst_h}: every side must be at least 1")
+        return tuple(b)
+
+    def resample_table(self, n_in: int, n_out: int) -> torch.Tensor:
+        """Pillow's LANCZOS weight table for one axis (built on the host by the library), in device memory; least recently used out"""
+        tabs = self.__dict__.setdefault("_resample_tables", {})
+        t = tabs.pop((n_in, n_out), None)
+        if t is None:
+            nbytes = int(self.ctx.lib.vsd_resample_table_bytes(int(n_in), int(n_out)))
+            if nbytes <= 0:
+                raise RuntimeError(f"resample: {n_in} -> {n_out}: lengths must be 1..{L.RESAMPLE_MAX_SIDE}")
+            with torch.cuda.stream(self.stream):
+                t = torch.empty(nbytes // 4, dtype=torch.int32, device=self.device)
+            self.ctx.call("vsd_resample_table_upload", int(n_in), int(n_out), self._p(t), self.raw_stream(0))
+            while len(tabs) >= self.RESAMPLE_TABLES:
+                tabs.pop(next(iter(tabs)))
+        tabs[(n_in, n_out)] = t
+        return t
+
+    def resample_rgb(self, src_u8, src_h, src_w, src_row_bytes, box, dst_u8, dst_h, dst_w):
+        """`img.crop(box).resize((dst_w, dst_h), LANCZOS)` of packed u8 RGB rows in device memory into dst_u8 [dst_h][dst_w][3],
+        bit for bit Pillow's (csrc/resample.hip)"""
+        bw, bh = int(box[2]) - int(box[0]), int(box[3]) - int(box[1])
+        tx = self.resample_table(bw, dst_w) if bw != dst_w and bw > 0 else None
+        ty = self.resample_table(bh, dst_h) if bh != dst_h and bh > 0 else None
+        ws = self.workspace("resample", int(self.ctx.lib.vsd_resample_workspace_bytes(bh, dst_w))) if tx is not None and ty is not None else None
+        self.ctx.call("vsd_resample_rgb", self._p(src_u8), int(src_h), int(src_w), int(src_row_bytes), (C.c_int * 4)(*[int(v) for v in box]),
+                      self._p(dst_u8), int(dst_h), int(dst_w), self._p(tx), self._p(ty), self._p(ws), self.s)
+
     def preprocess_rgb(self, rgb_u8, h, w, out):
         self.ctx.call("vsd_preprocess_rgb", self._p(rgb_u8), h, w, self._p(out), self.s)
 

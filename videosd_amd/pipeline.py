@@ -64,6 +64,10 @@ class VideoSDPipeline:
         self.honor_ref_flag = bool(kwargs.get("honor_ref_flag", False))
         self._ref_img = None
         self._ref_epoch = 0
+        # extension, off by default (a server should turn it on): the centre crop + LANCZOS resize in front of every
+        # frame (videopipeline.py:92-107) runs on the GPU instead of in PIL on this host thread -- the same bytes (csrc/resample.hip).
+        # RGB frames whose target size is a multiple of 8 take it; everything else keeps the host path.
+        self.device_resize = bool(kwargs.get("device_resize", False))
         # launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on
         # launch stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch
         self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
@@ -373,7 +377,9 @@ class VideoSDPipeline:
         if not 0 <= int(lane) < self.max_lanes:
             raise ValueError(f"lane {lane}: this pipeline was built for {self.max_lanes} launch lane(s) (kwarg `lanes`)")
         t0 = time.perf_counter()
-        imgs = [center_crop_resize(im, width, height) for im in imgs]
+        raw = self._raw_frames(imgs, width, height) if self.device_resize else None
+        if raw is None:
+            imgs = [center_crop_resize(im, width, height) for im in imgs]
         # A size that is not a multiple of the VAE stride: `VaeImageProcessor.preprocess` (lcm_controlnet.py:457, 230) rounds it
         # DOWN to a multiple of 8 with a Lanczos resize and the pipeline returns that size.  (There the control image is the
         # Sobel map of the unrounded frame, resized; here it is the Sobel map of the rounded frame -- sizes the client offers
@@ -393,7 +399,7 @@ class VideoSDPipeline:
                 raise ValueError("ref=True: one frame per call (the reference-only program runs one frame per launch)")
             use_cn = False  # the reference-only pipeline has no ControlNet (lcm_reference_pipeline.py:855-890)
             if self._ref_img is None:
-                self._ref_img = imgs[0]
+                self._ref_img = imgs[0] if raw is None else center_crop_resize(imgs[0], width, height)  # (stored as the host path stores it)
                 self._ref_epoch += 1
         # The captured program depends on the frame size, the NUMBER of timesteps and the ControlNet switch; `strength`
         # and `controlnet_scale` only change constants the graph reads from device memory (Engine.update_options): a
@@ -412,12 +418,30 @@ class VideoSDPipeline:
             eng._ref_epoch = self._ref_epoch
         np.random.seed(seed)  # kept for parity with videopipeline.py:112 (nothing downstream consumes it)
         t0 = time.perf_counter()
-        frames = np.stack([np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8) for im in imgs])
-        eng.submit_u8(frames[0] if len(imgs) == 1 else frames, overlap=self._overlap_now(lane))
+        if raw is not None:
+            eng.submit_raw_u8(raw[0] if len(raw) == 1 else raw, overlap=self._overlap_now(lane))
+        else:
+            frames = np.stack([np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8) for im in imgs])
+            eng.submit_u8(frames[0] if len(imgs) == 1 else frames, overlap=self._overlap_now(lane))
         self._outstanding.append(eng)
         self._lanes_busy.append(int(lane))
         self._note("upload_enqueue", t0)
         return (eng, len(imgs))
+
+    def _raw_frames(self, imgs, width: int, height: int):
+        """`device_resize`: the frames as uint8 [h][w][3] arrays for `Engine.submit_raw_u8`, or None when this call keeps the host
+        path: a frame that is not RGB, a target size that is not a multiple of 8 (the second Lanczos step below), a side the
+        kernel refuses, an ops object without the kernel."""
+        from .lib import RESAMPLE_MAX_SIDE
+
+        if height % 8 or width % 8 or height <= 0 or width <= 0 or not hasattr(getattr(self.model, "ops", None), "resample_rgb"):
+            return None
+        if max(height, width) > RESAMPLE_MAX_SIDE:
+            return None
+        for im in imgs:
+            if getattr(im, "mode", None) != "RGB" or min(im.size) < 1 or max(im.size) > RESAMPLE_MAX_SIDE:
+                return None
+        return [np.asarray(im, dtype=np.uint8) for im in imgs]
 
     def _overlap_now(self, lane: int) -> bool:
         """ONE policy for every caller (bench.py's engine legs follow the same rule): a launch runs its ControlNet encoder on

@@ -225,6 +225,17 @@ class CPlan:
         self.ctx.call("vsd_plan_infer", self.h, frame.ctypes.data, out.ctypes.data)
         return out
 
+    def infer_frame(self, frame: np.ndarray) -> np.ndarray:
+        """vsd_plan_infer_frame: camera frame(s) of any size, uint8 [h][w][3] ([batch][h][w][3] of one size), cropped and resampled on the device"""
+        nd = 3 if self.batch == 1 else 4
+        if frame.dtype != np.uint8 or frame.ndim != nd or frame.shape[-1] != 3 or (nd == 4 and frame.shape[0] != self.batch):
+            raise ValueError("frame must be uint8 [h][w][3]" if nd == 3 else f"frames must be uint8 [{self.batch}][h][w][3]")
+        frame = np.ascontiguousarray(frame)
+        out = np.empty((self.H, self.W, 3) if self.batch == 1 else (self.batch, self.H, self.W, 3), np.uint8)
+        h, w = frame.shape[-3], frame.shape[-2]
+        self.ctx.call("vsd_plan_infer_frame", self.h, frame.ctypes.data, h, w, 3 * w, out.ctypes.data)
+        return out
+
     def load_prompt(self, path: str):
         self.ctx.call("vsd_plan_load_prompt", self.h, path.encode())
 
