@@ -54,7 +54,7 @@ enum vsd_family {
 /* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
-#define VSD_VERSION 7
+#define VSD_VERSION 8
 int vsd_version(void);
 int vsd_conv_desc_size(void);
 
@@ -308,6 +308,40 @@ int64_t vsd_resample_workspace_bytes(int box_h, int dst_w);
 int vsd_resample_rgb(vsd_ctx* ctx, const void* src_u8, int src_h, int src_w, int64_t src_row_bytes, const int* box, void* dst_u8,
                      int dst_h, int dst_w, const void* table_x, const void* table_y, void* workspace, void* stream);
 
+/* ---- planar YUV 4:2:0 ("I420") <-> packed RGB: the frames of a WebRTC loop, converted on the device (csrc/yuv.hip) -----------------
+ * A decoded WebRTC frame is yuv420p and its encoder takes yuv420p again; the reference converts on the host around every frame
+ * (server.py:108 `frame.to_image()`, server.py:117 `VideoFrame.from_image`).  With these a frame crosses host <-> device as I420,
+ * 1.5 bytes per pixel instead of 3.
+ * THE COLOUR CONTRACT (fixed; host loops, kernels and tests are held to it byte for byte): 8 bits, BT.601 studio range
+ * (Y 16..235, chroma 16..240), the widely published integer form, 32-bit integers, >> arithmetic:
+ *   I420 -> RGB, C = Y - 16, D = U - 128, E = V - 128:
+ *     R = clamp((298 C + 409 E + 128) >> 8), G = clamp((298 C - 100 D - 208 E + 128) >> 8), B = clamp((298 C + 516 D + 128) >> 8)
+ *     pixel (x, y) of the frame takes chroma sample (x >> 1, y >> 1): no chroma interpolation.  Y is h x w, U and V are
+ *     ceil(h / 2) x ceil(w / 2); odd sizes are legal on input.
+ *   RGB -> I420 (even sizes only): Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel; per 2 x 2 block and channel
+ *     m = (p00 + p01 + p10 + p11 + 2) >> 2, then U = ((-38 mR - 74 mG + 112 mB + 128) >> 8) + 128,
+ *     V = ((112 mR - 94 mG - 18 mB + 128) >> 8) + 128 (no clamp needed: the results stay inside 16..240).
+ *   The integer form is within 1 LSB per channel of the real-valued BT.601 matrix.  It is NOT claimed to equal libswscale's bytes:
+ *   how far swscale's tables are from it is not measured.  There is no entry point for full-range (yuvj420p), NV12, 4:2:2 / 4:4:4,
+ *   more than 8 bits or BT.709: a caller holding such a frame must convert it first (the Python layer refuses them by name).
+ * vsd_i420_to_rgb: an h x w rectangle whose first luma sample sits at frame position (ox, oy), of which only the parities matter:
+ *   pixel (j, i) of the rectangle reads y[i * y_stride + j] and chroma [((oy & 1) + i) >> 1][((ox & 1) + j) >> 1] of the u / v pointers
+ *   given (they point at chroma sample (ox >> 1, oy >> 1) of the frame) -- a crop box with an odd left / top edge converts to the bytes
+ *   of "convert the whole frame, then crop".  dst_rgb: packed RGB rows of dst_row_bytes >= 3 w bytes, the layout vsd_resample_rgb and
+ *   vsd_preprocess_rgb read.
+ * vsd_rgb_to_i420: packed [h][w][3] (the engine's output frame) into three planes; h and w even.
+ * Sides 1..VSD_RESAMPLE_MAX_SIDE; null pointers, short strides, odd output sizes and overlapping source / destination are refused with
+ *   VSD_ERR_ARG and a reason.  One launch each; dword-wide loads and stores when pointers, strides (and for vsd_rgb_to_i420 the width)
+ *   are multiples of 4, a byte-wide form otherwise -- the same bytes.
+ * The _host twins: the same arithmetic as plain host loops, no GPU and no context needed (VSD_ERR_ARG without a message). */
+int vsd_i420_to_rgb(vsd_ctx* ctx, const void* y, int64_t y_stride, const void* u, const void* v, int64_t uv_stride, int ox, int oy, int h, int w,
+                    void* dst_rgb, int64_t dst_row_bytes, void* stream);
+int vsd_rgb_to_i420(vsd_ctx* ctx, const void* rgb_u8, int h, int w, void* dst_y, void* dst_u, void* dst_v, int64_t y_stride, int64_t uv_stride,
+                    void* stream);
+int vsd_i420_to_rgb_host(const void* y, int64_t y_stride, const void* u, const void* v, int64_t uv_stride, int ox, int oy, int h, int w,
+                         void* dst_rgb, int64_t dst_row_bytes);
+int vsd_rgb_to_i420_host(const void* rgb_u8, int h, int w, void* dst_y, void* dst_u, void* dst_v, int64_t y_stride, int64_t uv_stride);
+
 /* ---- two independent operations as ONE grid per kernel ------------------------------------------------
  * The reference runs the ControlNet and then the UNet encoder of a denoising step -- the same topology with two weight sets on the
  * same latents (lcm_controlnet.py:539-577) -- as two sequences of cuDNN / cuBLAS launches.  Here the two walk in lock step:
@@ -347,6 +381,16 @@ int vsd_plan_infer(vsd_ctx* ctx, vsd_plan* plan, const void* frame_u8_host, void
  * A new source size costs two tables, not a new plan.  Sizes: as for vsd_resample_rgb. */
 int vsd_plan_submit_frame(vsd_ctx* ctx, vsd_plan* plan, const void* src_u8_host, int src_h, int src_w, int64_t src_row_bytes, void* out_u8_host);
 int vsd_plan_infer_frame(vsd_ctx* ctx, vsd_plan* plan, const void* src_u8_host, int src_h, int src_w, int64_t src_row_bytes, void* out_u8_host);
+/* The I420 twins: the camera frame as three planes on the host (y rows of y_stride bytes, u and v rows of uv_stride bytes, any size,
+ * odd sizes included; frames per launch > 1: that many frames of this one size, src_h * y_stride resp. ceil(src_h / 2) * uv_stride bytes
+ * apart), the result as PACKED I420 (per frame H * W bytes of Y, then H * W / 4 of U, then of V: H * W * 3 / 2 bytes, H and W even) in
+ * out_i420_host when vsd_plan_wait returns.  Crop box of vsd_center_crop_box; upload of the box's plane rectangles alone (widened to
+ * an even left / top edge); vsd_i420_to_rgb; vsd_resample_rgb into the plan's input frame; graph launch; vsd_rgb_to_i420 behind it.
+ * Not part of a plan FILE: the plan format does not change. */
+int vsd_plan_submit_frame_i420(vsd_ctx* ctx, vsd_plan* plan, const void* y_host, int64_t y_stride, const void* u_host, const void* v_host,
+                               int64_t uv_stride, int src_h, int src_w, void* out_i420_host);
+int vsd_plan_infer_frame_i420(vsd_ctx* ctx, vsd_plan* plan, const void* y_host, int64_t y_stride, const void* u_host, const void* v_host,
+                              int64_t uv_stride, int src_h, int src_w, void* out_i420_host);
 /* another prompt for a loaded plan: a file written by videosd_amd.plan.export_prompt (the prompt's constant block, same layout) */
 int vsd_plan_load_prompt(vsd_ctx* ctx, vsd_plan* plan, const char* path);
 void vsd_plan_free(vsd_ctx* ctx, vsd_plan* plan);

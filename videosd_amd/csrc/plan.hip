@@ -43,6 +43,9 @@ struct vsd_plan {
   void *raw = nullptr, *work = nullptr, *table_x = nullptr, *table_y = nullptr;
   size_t raw_bytes = 0, work_bytes = 0;
   int table_x_in = 0, table_y_in = 0;
+  // I420 camera frames (vsd_plan_submit_frame_i420): the uploaded plane rectangles and the packed I420 result
+  void *yuv_in = nullptr, *yuv_out = nullptr;
+  size_t yuv_in_bytes = 0, yuv_out_bytes = 0;
 };
 
 namespace {
@@ -75,9 +78,34 @@ void plan_release(vsd_plan* p) {
   if (p->stream && p->own_stream) (void)hipStreamDestroy(p->stream);
   for (void* r : p->regions)
     if (r) (void)hipFree(r);
-  for (void* r : {p->raw, p->work, p->table_x, p->table_y})
+  for (void* r : {p->raw, p->work, p->table_x, p->table_y, p->yuv_in, p->yuv_out})
     if (r) (void)hipFree(r);
   delete p;
+}
+
+// a device buffer of the plan grown to `need` bytes (never shrunk); waits for the plan's stream first: nothing in flight reads the old one
+int plan_grow(vsd_ctx* ctx, vsd_plan* plan, const char* who, void** p, size_t* have, size_t need) {
+  if (*have >= need) return VSD_OK;
+  VSD_HIP(ctx, hipStreamSynchronize(plan->stream));
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  if (hipMalloc(p, need) != hipSuccess) return vsd_fail(ctx, VSD_ERR_NOMEM, "%s: out of device memory (%zu bytes)", who, need);
+  *have = need;
+  return VSD_OK;
+}
+
+// the plan's table of one axis for another source length
+int plan_table(vsd_ctx* ctx, vsd_plan* plan, const char* who, void** t, int* have_in, int in, int out) {
+  if (in == out || *have_in == in) return VSD_OK;
+  VSD_HIP(ctx, hipStreamSynchronize(plan->stream));
+  if (*t) (void)hipFree(*t);
+  *t = nullptr;
+  *have_in = 0;
+  if (hipMalloc(t, (size_t)vsd_resample_table_bytes(in, out)) != hipSuccess) return vsd_fail(ctx, VSD_ERR_NOMEM, "%s: out of device memory (table)", who);
+  const int rc = vsd_resample_table_upload(ctx, in, out, *t, (void*)plan->stream);
+  if (rc == VSD_OK) *have_in = in;
+  return rc;
 }
 
 }  // namespace
@@ -273,31 +301,11 @@ extern "C" int vsd_plan_submit_frame(vsd_ctx* ctx, vsd_plan* plan, const void* s
       VSD_HIP(ctx, hipMemcpy2DAsync((char*)plan->in + b * frame, row, src + (size_t)b * src_h * src_row_bytes, (size_t)src_row_bytes, row, (size_t)bh,
                                     hipMemcpyHostToDevice, plan->stream));
   } else {
-    auto grow = [&](void** p, size_t* have, size_t need) -> int {
-      if (*have >= need) return VSD_OK;
-      VSD_HIP(ctx, hipStreamSynchronize(plan->stream));  // (nothing in flight reads the old buffer)
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-      *have = 0;
-      if (hipMalloc(p, need) != hipSuccess) return vsd_fail(ctx, VSD_ERR_NOMEM, "plan_submit_frame: out of device memory (%zu bytes)", need);
-      *have = need;
-      return VSD_OK;
-    };
-    auto table = [&](void** t, int* have_in, int in, int out) -> int {
-      if (in == out || *have_in == in) return VSD_OK;
-      VSD_HIP(ctx, hipStreamSynchronize(plan->stream));
-      if (*t) (void)hipFree(*t);
-      *t = nullptr;
-      *have_in = 0;
-      if (hipMalloc(t, (size_t)vsd_resample_table_bytes(in, out)) != hipSuccess) return vsd_fail(ctx, VSD_ERR_NOMEM, "plan_submit_frame: out of device memory (table)");
-      const int rc = vsd_resample_table_upload(ctx, in, out, *t, (void*)plan->stream);
-      if (rc == VSD_OK) *have_in = in;
-      return rc;
-    };
-    int rc = grow(&plan->raw, &plan->raw_bytes, one * plan->batch);
-    if (rc == VSD_OK) rc = grow(&plan->work, &plan->work_bytes, (size_t)vsd_resample_workspace_bytes(bh, plan->W));
-    if (rc == VSD_OK) rc = table(&plan->table_x, &plan->table_x_in, bw, plan->W);
-    if (rc == VSD_OK) rc = table(&plan->table_y, &plan->table_y_in, bh, plan->H);
+    const char* who = "plan_submit_frame";
+    int rc = plan_grow(ctx, plan, who, &plan->raw, &plan->raw_bytes, one * plan->batch);
+    if (rc == VSD_OK) rc = plan_grow(ctx, plan, who, &plan->work, &plan->work_bytes, (size_t)vsd_resample_workspace_bytes(bh, plan->W));
+    if (rc == VSD_OK) rc = plan_table(ctx, plan, who, &plan->table_x, &plan->table_x_in, bw, plan->W);
+    if (rc == VSD_OK) rc = plan_table(ctx, plan, who, &plan->table_y, &plan->table_y_in, bh, plan->H);
     if (rc != VSD_OK) return rc;
     const int whole[4] = {0, 0, bw, bh};
     for (int b = 0; b < plan->batch; ++b) {
@@ -315,6 +323,76 @@ extern "C" int vsd_plan_submit_frame(vsd_ctx* ctx, vsd_plan* plan, const void* s
 
 extern "C" int vsd_plan_infer_frame(vsd_ctx* ctx, vsd_plan* plan, const void* src_u8_host, int src_h, int src_w, int64_t src_row_bytes, void* out_u8_host) {
   const int rc = vsd_plan_submit_frame(ctx, plan, src_u8_host, src_h, src_w, src_row_bytes, out_u8_host);
+  return rc != VSD_OK ? rc : vsd_plan_wait(ctx, plan);
+}
+
+// The I420 twin: the camera frame arrives as three planes and the result leaves as packed I420 -- half the bytes both ways.  Only the
+// plane rectangles of the crop box travel (widened to an even left / top edge, so that the rectangle starts on a chroma sample and
+// the conversion runs in its dword-wide form); the box's odd edge is then the resample's box inside the converted rectangle: the bytes
+// of "convert the whole frame, crop, resize".  Conversions and resample are ordinary launches around the captured graph.
+extern "C" int vsd_plan_submit_frame_i420(vsd_ctx* ctx, vsd_plan* plan, const void* y_host, int64_t y_stride, const void* u_host, const void* v_host,
+                                          int64_t uv_stride, int src_h, int src_w, void* out_i420_host) {
+  if (!ctx || !plan || !y_host || !u_host || !v_host || !out_i420_host) return VSD_ERR_ARG;
+  const char* who = "plan_submit_frame_i420";
+  if (src_h < 1 || src_w < 1 || src_h > VSD_RESAMPLE_MAX_SIDE || src_w > VSD_RESAMPLE_MAX_SIDE || y_stride < src_w || uv_stride < (src_w + 1) / 2)
+    return vsd_fail(ctx, VSD_ERR_ARG, "%s: a %d x %d source with rows of %lld / %lld bytes (sides 1..%d, rows of at least width / ceil(width / 2) bytes)", who, src_w,
+                    src_h, (long long)y_stride, (long long)uv_stride, VSD_RESAMPLE_MAX_SIDE);
+  if ((plan->H | plan->W) & 1) return vsd_fail(ctx, VSD_ERR_ARG, "%s: the plan's %d x %d frame has an odd side: no 4:2:0 output", who, plan->W, plan->H);
+  int box[4];
+  if (vsd_center_crop_box(src_w, src_h, plan->W, plan->H, box) != VSD_OK) return vsd_fail(ctx, VSD_ERR_ARG, "%s: no crop box", who);
+  const int bw = box[2] - box[0], bh = box[3] - box[1];
+  if (box[0] < 0 || box[1] < 0 || bw < 1 || bh < 1 || box[2] > src_w || box[3] > src_h)
+    return vsd_fail(ctx, VSD_ERR_ARG, "%s: the crop box of a %d x %d source for %d x %d is empty", who, src_w, src_h, plan->W, plan->H);
+  const int el = box[0] & ~1, et = box[1] & ~1;            // the uploaded rectangle: even left / top edge
+  const int rw = box[2] - el, rh = box[3] - et;            // its luma size
+  const int cw = (rw + 1) / 2, ch = (rh + 1) / 2;          // its chroma size
+  const size_t ys = ((size_t)rw + 3) & ~(size_t)3, cs = ((size_t)cw + 3) & ~(size_t)3;  // device rows: multiples of 4 bytes
+  const size_t one_in = (ys * rh + 2 * cs * ch + 255) & ~(size_t)255;
+  const size_t row = ((size_t)rw * 3 + 3) & ~(size_t)3, one_rgb = (row * rh + 255) & ~(size_t)255;
+  const size_t frame = (size_t)plan->H * plan->W * 3, frame420 = frame / 2;
+  const bool direct = bw == plan->W && bh == plan->H && el == box[0] && et == box[1];  // already the target size: convert into the input frame
+  int rc = plan_grow(ctx, plan, who, &plan->yuv_in, &plan->yuv_in_bytes, one_in * plan->batch);
+  if (rc == VSD_OK) rc = plan_grow(ctx, plan, who, &plan->yuv_out, &plan->yuv_out_bytes, frame420 * plan->batch);
+  if (rc == VSD_OK && !direct) rc = plan_grow(ctx, plan, who, &plan->raw, &plan->raw_bytes, one_rgb * plan->batch);
+  if (rc == VSD_OK && !direct) rc = plan_grow(ctx, plan, who, &plan->work, &plan->work_bytes, (size_t)vsd_resample_workspace_bytes(bh, plan->W));
+  if (rc == VSD_OK) rc = plan_table(ctx, plan, who, &plan->table_x, &plan->table_x_in, bw, plan->W);
+  if (rc == VSD_OK) rc = plan_table(ctx, plan, who, &plan->table_y, &plan->table_y_in, bh, plan->H);
+  if (rc != VSD_OK) return rc;
+  const int inner[4] = {box[0] - el, box[1] - et, box[0] - el + bw, box[1] - et + bh};
+  const size_t src_ch = ((size_t)src_h + 1) / 2;
+  for (int b = 0; b < plan->batch; ++b) {
+    const unsigned char* hy = (const unsigned char*)y_host + ((size_t)b * src_h + et) * y_stride + el;
+    const unsigned char* hu = (const unsigned char*)u_host + ((size_t)b * src_ch + et / 2) * uv_stride + el / 2;
+    const unsigned char* hv = (const unsigned char*)v_host + ((size_t)b * src_ch + et / 2) * uv_stride + el / 2;
+    unsigned char* dy = (unsigned char*)plan->yuv_in + b * one_in;
+    unsigned char *du = dy + ys * rh, *dv = du + cs * ch;
+    VSD_HIP(ctx, hipMemcpy2DAsync(dy, ys, hy, (size_t)y_stride, (size_t)rw, (size_t)rh, hipMemcpyHostToDevice, plan->stream));
+    VSD_HIP(ctx, hipMemcpy2DAsync(du, cs, hu, (size_t)uv_stride, (size_t)cw, (size_t)ch, hipMemcpyHostToDevice, plan->stream));
+    VSD_HIP(ctx, hipMemcpy2DAsync(dv, cs, hv, (size_t)uv_stride, (size_t)cw, (size_t)ch, hipMemcpyHostToDevice, plan->stream));
+    if (direct) {
+      rc = vsd_i420_to_rgb(ctx, dy, (int64_t)ys, du, dv, (int64_t)cs, 0, 0, rh, rw, (char*)plan->in + b * frame, (int64_t)plan->W * 3, (void*)plan->stream);
+    } else {
+      rc = vsd_i420_to_rgb(ctx, dy, (int64_t)ys, du, dv, (int64_t)cs, 0, 0, rh, rw, (char*)plan->raw + b * one_rgb, (int64_t)row, (void*)plan->stream);
+      if (rc == VSD_OK)
+        rc = vsd_resample_rgb(ctx, (char*)plan->raw + b * one_rgb, rh, rw, (int64_t)row, inner, (char*)plan->in + b * frame, plan->H, plan->W, plan->table_x,
+                              plan->table_y, plan->work, (void*)plan->stream);
+    }
+    if (rc != VSD_OK) return rc;
+  }
+  VSD_HIP(ctx, hipGraphLaunch((hipGraphExec_t)plan->graph, plan->stream));
+  const size_t ysz = (size_t)plan->H * plan->W;
+  for (int b = 0; b < plan->batch; ++b) {
+    unsigned char* o = (unsigned char*)plan->yuv_out + b * frame420;
+    rc = vsd_rgb_to_i420(ctx, (char*)plan->out + b * frame, plan->H, plan->W, o, o + ysz, o + ysz + ysz / 4, plan->W, plan->W / 2, (void*)plan->stream);
+    if (rc != VSD_OK) return rc;
+  }
+  VSD_HIP(ctx, hipMemcpyAsync(out_i420_host, plan->yuv_out, frame420 * plan->batch, hipMemcpyDeviceToHost, plan->stream));
+  return VSD_OK;
+}
+
+extern "C" int vsd_plan_infer_frame_i420(vsd_ctx* ctx, vsd_plan* plan, const void* y_host, int64_t y_stride, const void* u_host, const void* v_host,
+                                         int64_t uv_stride, int src_h, int src_w, void* out_i420_host) {
+  const int rc = vsd_plan_submit_frame_i420(ctx, plan, y_host, y_stride, u_host, v_host, uv_stride, src_h, src_w, out_i420_host);
   return rc != VSD_OK ? rc : vsd_plan_wait(ctx, plan);
 }
 

@@ -33,6 +33,8 @@ from typing import Any, Callable, Dict, List, Optional
 
 import torch
 
+from .frames import I420Frame, av_plane_views, is_i420
+
 
 # ----------------------------------------------------------------------------------------- frame sharding
 def shard_indices(n_frames: int, rank: int, world: int) -> List[int]:
@@ -207,6 +209,25 @@ def _image_to_slot(ring: _ShmRing, slot: int, img) -> Optional[tuple]:
     return (slot, w, h)
 
 
+def _i420_to_slot(ring: _ShmRing, slot: int, planes, w: int, h: int) -> tuple:
+    """Three plane views (an `I420Frame`'s, or `frames.av_plane_views` of an av frame: padded `line_size` rows read in place, once) into a
+    slot as packed I420 -- Y, U, V, rows tight: 1.5 bytes per pixel where RGB has 3.  Plane copies only, no arithmetic (numpy row
+    copies, GIL released).  The caller has checked that the frame fits the slot."""
+    import numpy as np
+
+    dst = I420Frame(np.frombuffer(ring.view(slot, I420Frame.nbytes_for(w, h)), dtype=np.uint8), w, h)
+    dst.y[...], dst.u[...], dst.v[...] = planes
+    return (slot, w, h)
+
+
+def _i420_from_slot(ring: _ShmRing, slot: int, w: int, h: int, copy: bool):
+    """copy=False: the frame's planes are views of the slot (the worker: the request slot is held until the reply)"""
+    import numpy as np
+
+    a = np.frombuffer(ring.view(slot, I420Frame.nbytes_for(w, h)), dtype=np.uint8)
+    return I420Frame(a.copy() if copy else a, w, h)
+
+
 # ----------------------------------------------------------------------------------------- worker process
 def _resolve(path: str) -> Callable:
     mod, _, name = path.partition(":")
@@ -310,6 +331,9 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
     epoch = 0
 
     def reply(rid, img, slot):
+        if rings is not None and slot is not None and isinstance(img, I420Frame) and img.data.size <= rings[1].slot_bytes:
+            conn.send((rid, True, ("__shm420__",) + _i420_to_slot(rings[1], slot, (img.y, img.u, img.v), img.width, img.height)))
+            return
         if rings is not None and slot is not None and hasattr(img, "tobytes"):
             where = _image_to_slot(rings[1], slot, img)
             if where is not None:
@@ -345,6 +369,9 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
         if method == "infer" and len(args) == 1 and isinstance(args[0], tuple) and args[0] and args[0][0] == "__shm__":
             _, slot, w, h = args[0]
             args = (_image_from_slot(rings[0], slot, w, h, copy=False),)
+        elif method == "infer" and len(args) == 1 and isinstance(args[0], tuple) and args[0] and args[0][0] == "__shm420__":
+            _, slot, w, h = args[0]
+            args = (_i420_from_slot(rings[0], slot, w, h, copy=False),)
         return rid, method, args, kwargs, slot
 
     def sync_prompt(prompt, header, collective=True):
@@ -798,6 +825,10 @@ class RemotePipeline:
             _, s, w, h = payload
             payload = _image_from_slot(self._rings[1], s, w, h, copy=True)
             self.host_s["frames"] += 1
+        elif ok and isinstance(payload, tuple) and payload and payload[0] == "__shm420__":
+            _, s, w, h = payload
+            payload = _i420_from_slot(self._rings[1], s, w, h, copy=True)
+            self.host_s["frames"] += 1
         t1 = time.perf_counter()
         self.host_s["slot_read"] += t1 - t0
         if slot is not None:
@@ -859,7 +890,23 @@ class RemotePipeline:
         if not self._ready:
             self.wait_ready()
         slot = None
-        if name == "infer" and self._rings is not None and len(args) == 1 and hasattr(args[0], "tobytes") and hasattr(args[0], "size"):
+        if name == "infer" and len(args) == 1 and is_i420(args[0]):
+            # a WebRTC frame crosses as I420: the three planes go straight into the request slot (two plane copies per frame in this
+            # process, out and back, and no arithmetic); too large for a slot or no slot free: pickled as an I420Frame.  The frame is
+            # checked BEFORE a slot is taken (another pixel format, a short plane: ValueError to the caller, no slot held).
+            f = args[0]
+            planes = (f.y, f.u, f.v) if isinstance(f, I420Frame) else av_plane_views(f)
+            h, w = planes[0].shape
+            if self._rings is not None and I420Frame.nbytes_for(w, h) <= self._rings[0].slot_bytes:
+                with self._lock:
+                    slot = self._free_slots.pop() if self._free_slots else None
+            if slot is not None:
+                t0 = time.perf_counter()
+                args = (("__shm420__",) + _i420_to_slot(self._rings[0], slot, planes, w, h),)
+                self.host_s["slot_write"] += time.perf_counter() - t0
+            else:
+                args = (f if isinstance(f, I420Frame) else I420Frame.from_planes(*planes),)
+        elif name == "infer" and self._rings is not None and len(args) == 1 and hasattr(args[0], "tobytes") and hasattr(args[0], "size"):
             with self._lock:
                 slot = self._free_slots.pop() if self._free_slots else None
             if slot is not None:

@@ -1579,6 +1579,106 @@ class Engine:
         self.submit_raw_u8(frame)
         return self.collect_u8()
 
+    def submit_raw_i420(self, frame, overlap: Optional[bool] = None):
+        """`submit_raw_u8` for planar YUV 4:2:0 camera frames (`frames.I420Frame`, any size, odd sizes included; prepared with batch
+        B > 1: a list of B frames, possibly of different sizes).  Per frame: the reference's crop box on the full frame size, widened
+        to an even left / top edge so that it starts on a chroma sample; only those plane rectangles are copied into the pinned
+        staging and uploaded (1.5 bytes per pixel); `i420_to_rgb` into device scratch (straight into `frame_u8` when the box already
+        has the plan's size), `resample_rgb` of the box inside that rectangle into `frame_u8`; then `launch`.  The bytes of "convert
+        the whole frame by the colour contract (include/vsd.h), crop, LANCZOS-resize with PIL"."""
+        from .frames import I420Frame
+
+        p = self.plan
+        H, W, B = p["H"], p["W"], p["batch"]
+        frames = [frame] if B == 1 and isinstance(frame, I420Frame) else list(frame)
+        if len(frames) != B:
+            raise ValueError(f"this engine takes {B} frame(s) per launch, got {len(frames)}")
+        rects, total, scratch = [], 0, 0
+        for f in frames:
+            if not isinstance(f, I420Frame):
+                raise ValueError(f"frame must be an I420Frame, got {type(f).__name__}")
+            l, t, r, b = self.ops.center_crop_box(f.width, f.height, W, H)
+            if not (0 <= l < r <= f.width and 0 <= t < b <= f.height):
+                raise ValueError(f"the crop box of a {f.width} x {f.height} frame for {W} x {H} is empty")
+            el, et = l & ~1, t & ~1
+            rw, rh = r - el, b - et
+            cw, ch = (rw + 1) // 2, (rh + 1) // 2
+            ys, cs = _ru(rw, 4), _ru(cw, 4)  # (device rows start on a dword: the conversion's dword-wide form)
+            rects.append((l, t, r, b, el, et, rw, rh, cw, ch, ys, cs, total))
+            total += _ru(ys * rh + 2 * cs * ch, 256)
+            if not ((r - l, b - t) == (W, H) and (el, et) == (l, t)):
+                scratch = max(scratch, _ru(rw * 3, 4) * rh)
+        hraw, draw = self._raw_staging(total)
+        rgb = self.ops.workspace("i420_rgb", scratch) if scratch else None
+        _, _hin, _hout, e0, e1 = self._staging()
+        hb = hraw.numpy()
+        for i, (f, (l, t, r, b, el, et, rw, rh, cw, ch, ys, cs, off)) in enumerate(zip(frames, rects)):
+            ou, ov = off + ys * rh, off + ys * rh + cs * ch
+            hb[off:ou].reshape(rh, ys)[:, :rw] = f.y[et:b, el:r]  # (only the crop box's plane rectangles travel)
+            hb[ou:ov].reshape(ch, cs)[:, :cw] = f.u[et // 2:et // 2 + ch, el // 2:el // 2 + cw]
+            hb[ov:ov + cs * ch].reshape(ch, cs)[:, :cw] = f.v[et // 2:et // 2 + ch, el // 2:el // 2 + cw]
+            n = ys * rh + 2 * cs * ch
+            self.ops.upload(draw[off:off + n], hraw[off:off + n])
+            dst = self.frame_u8 if B == 1 else self.frame_u8[i]
+            dy, du, dv = draw[off:ou], draw[ou:ov], draw[ov:ov + cs * ch]
+            if (r - l, b - t) == (W, H) and (el, et) == (l, t):
+                self.ops.i420_to_rgb(dy, ys, du, dv, cs, 0, 0, rh, rw, dst, W * 3)
+            else:
+                row = _ru(rw * 3, 4)
+                self.ops.i420_to_rgb(dy, ys, du, dv, cs, 0, 0, rh, rw, rgb, row)
+                self.ops.resample_rgb(rgb, rh, rw, row, (l - el, t - et, r - el, b - et), dst, H, W)
+        self.last_upload_bytes = total  # (counted: what `upload` was handed; VideoSDPipeline.metrics reports it per frame)
+        if e0 is not None:
+            e0.record(self.ops.stream)
+        self.launch(overlap)
+        if e1 is not None:
+            e1.record(self.ops.stream)
+        self._enqueue_i420()  # (behind the captured program at submit, as vsd_plan_submit_frame_i420 does: nothing is launched at collect)
+
+    def _enqueue_i420(self):
+        """`rgb_to_i420` of `out_u8` on the lane's stream into a device buffer of this engine (packed I420 per frame)"""
+        p = self.plan
+        H, W, B = p["H"], p["W"], p["batch"]
+        if (H | W) & 1:
+            raise ValueError(f"I420 output: a {W} x {H} frame has an odd side")
+        one = H * W * 3 // 2
+        st = getattr(self, "_i420_stage", None)
+        if st is None or st[0].numel() != B * one:
+            st = (self.ops.empty(B * one, dtype=torch.uint8), torch.empty(B * one, dtype=torch.uint8, pin_memory=torch.cuda.is_available()))
+            self._i420_stage = st
+        dev = st[0]
+        for i in range(B):
+            o = i * one
+            src = self.out_u8 if B == 1 else self.out_u8[i]
+            self.ops.rgb_to_i420(src, H, W, dev[o:o + H * W], dev[o + H * W:o + H * W * 5 // 4], dev[o + H * W * 5 // 4:o + one])
+        self._i420_queued = True
+
+    def collect_i420(self):
+        """Wait for the frame(s) enqueued by the last submit and bring them to the host as I420, 1.5 bytes per pixel through pinned
+        memory.  After `submit_raw_i420` the conversion is already queued behind the program; after another submit it is launched here.
+        Returns an `I420Frame` (a list of B)."""
+        from .frames import I420Frame
+
+        p = self.plan
+        H, W, B = p["H"], p["W"], p["batch"]
+        if not getattr(self, "_i420_queued", False):
+            self._enqueue_i420()
+        self._i420_queued = False
+        dev, host = self._i420_stage
+        one = H * W * 3 // 2
+        _, _hin, _hout, e0, e1 = self._staging()
+        self.ops.download_into(host, dev)
+        self.last_download_bytes = B * one
+        if e0 is not None:
+            self.last_gpu_ms = e0.elapsed_time(e1)  # the graph alone, as `collect_u8` reports it
+        out = [I420Frame(host.numpy()[i * one:(i + 1) * one].copy(), W, H) for i in range(B)]
+        return out[0] if B == 1 else out
+
+    def infer_raw_i420(self, frame):
+        """I420 camera frame(s) of any size -> I420Frame(s) of the plan's size"""
+        self.submit_raw_i420(frame)
+        return self.collect_i420()
+
     def collect_u8(self) -> np.ndarray:
         """Wait for the frame(s) enqueued by the last `submit_u8` and bring them to the host (a fresh array)."""
         want = self._want_shape()

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # VSD_LIB: another build of the same sources (development: the instrumented libvsd_tl.so of build.build_timeline)
 LIB_PATH = os.environ.get("VSD_LIB") or os.path.join(HERE, "libvsd.so")
 
-VERSION = 7  # include/vsd.h VSD_VERSION
+VERSION = 8  # include/vsd.h VSD_VERSION
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GEGLU, ACT_QUICKGELU, ACT_SOFTMAX, ACT_GELU = range(7)
 ACT_POST = 256
 SPLITK_MAX_TILES = 16384
@@ -101,6 +101,11 @@ SIGNATURES = {
     "vsd_resample_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "vsd_resample_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vsd_i420_to_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "vsd_rgb_to_i420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "vsd_i420_to_rgb_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "vsd_rgb_to_i420_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     "vsd_graph_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vsd_graph_end": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "vsd_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -124,6 +129,8 @@ SIGNATURES = {
     "vsd_plan_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vsd_plan_submit_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
     "vsd_plan_infer_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "vsd_plan_submit_frame_i420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "vsd_plan_infer_frame_i420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "vsd_plan_load_prompt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p]),
     "vsd_plan_free": (None, [C.c_void_p, C.c_void_p]),
     "vsd_pinned_alloc": (C.c_void_p, [C.c_void_p, C.c_size_t]),

@@ -957,6 +957,17 @@ class HipOps:
         self.ctx.call("vsd_resample_rgb", self._p(src_u8), int(src_h), int(src_w), int(src_row_bytes), (C.c_int * 4)(*[int(v) for v in box]),
                       self._p(dst_u8), int(dst_h), int(dst_w), self._p(tx), self._p(ty), self._p(ws), self.s)
 
+    def i420_to_rgb(self, y, y_stride, u, v, uv_stride, ox, oy, h, w, dst_rgb, dst_row_bytes=None):
+        """An h x w rectangle of an I420 frame in device memory (first luma sample at frame position (ox, oy); u / v point at chroma
+        sample (ox >> 1, oy >> 1)) to packed RGB rows, by the colour contract of include/vsd.h (csrc/yuv.hip)"""
+        self.ctx.call("vsd_i420_to_rgb", self._p(y), int(y_stride), self._p(u), self._p(v), int(uv_stride), int(ox), int(oy), int(h), int(w),
+                      self._p(dst_rgb), int(3 * w if dst_row_bytes is None else dst_row_bytes), self.s)
+
+    def rgb_to_i420(self, rgb_u8, h, w, dst_y, dst_u, dst_v, y_stride=None, uv_stride=None):
+        """packed [h][w][3] in device memory (h, w even) to three planes, by the same contract"""
+        self.ctx.call("vsd_rgb_to_i420", self._p(rgb_u8), int(h), int(w), self._p(dst_y), self._p(dst_u), self._p(dst_v),
+                      int(w if y_stride is None else y_stride), int(w // 2 if uv_stride is None else uv_stride), self.s)
+
     def preprocess_rgb(self, rgb_u8, h, w, out):
         self.ctx.call("vsd_preprocess_rgb", self._p(rgb_u8), h, w, self._p(out), self.s)
 

@@ -21,6 +21,7 @@ from PIL import Image
 from . import config as C
 from . import checkpoints as CK
 from . import weights as W
+from .frames import I420Frame, is_i420
 
 
 def center_crop_resize(img: Image.Image, width: int, height: int) -> Image.Image:
@@ -96,8 +97,9 @@ class VideoSDPipeline:
         self.evictions = 0
         self._outstanding = []  # engines with a submitted, not yet collected launch
         self._lanes_busy = []   # ... and the lane each of them runs on
-        self._host_ms = {"crop_resize": [], "upload_enqueue": [], "wait_download": [], "to_pil": [], "gpu": [], "prepare": [], "update_options": [],
+        self._host_ms = {"crop_resize": [], "upload_enqueue": [], "wait_download": [], "to_pil": [], "to_i420": [], "gpu": [], "prepare": [], "update_options": [],
                          "prompt": []}
+        self._io_bytes = {"up": None, "down": None}  # per frame of the last launch submitted / collected
 
     # ------------------------------------------------------------------ model loading
     def load_model(self, model_name, controlnet_model="lllyasviel/control_v11p_sd15_canny"):
@@ -302,7 +304,7 @@ class VideoSDPipeline:
         out["prompts_cached"] = len(self._prompts)
         out["engines_evicted_for_memory"] = self.evictions
         free, total = torch.cuda.mem_get_info(int(self.device))  # what a leak across plan / prompt changes would show in
-        return {"stage_ms_p50": out, "device_free_mb": free >> 20, "device_total_mb": total >> 20,
+        return {"stage_ms_p50": out, "io_bytes_per_frame": dict(self._io_bytes), "device_free_mb": free >> 20, "device_total_mb": total >> 20,
                 "allocated_mb": torch.cuda.memory_allocated(int(self.device)) >> 20}
 
     def stage_profile(self, batch: int = 1):
@@ -377,8 +379,19 @@ class VideoSDPipeline:
         if not 0 <= int(lane) < self.max_lanes:
             raise ValueError(f"lane {lane}: this pipeline was built for {self.max_lanes} launch lane(s) (kwarg `lanes`)")
         t0 = time.perf_counter()
-        raw = self._raw_frames(imgs, width, height) if self.device_resize else None
-        if raw is None:
+        # WebRTC frames (planar YUV 4:2:0: an `I420Frame`, or an av.VideoFrame by duck typing): when EVERY frame of the launch is one,
+        # the planes go to the device as they are and the result comes back as I420 (`_i420_on_device`); otherwise such a frame is
+        # converted here by the host loop of the same colour contract and takes the path of a PIL image -- the same bytes either way.
+        yuv = [is_i420(im) for im in imgs]
+        i420 = None
+        if any(yuv):
+            imgs = [I420Frame.coerce(im) if k else im for im, k in zip(imgs, yuv)]
+            if all(yuv) and self._i420_on_device(imgs, width, height, ref):
+                i420 = imgs
+            else:
+                imgs = [Image.fromarray(im.to_rgb(), mode="RGB") if k else im for im, k in zip(imgs, yuv)]
+        raw = self._raw_frames(imgs, width, height) if self.device_resize and i420 is None else None
+        if raw is None and i420 is None:
             imgs = [center_crop_resize(im, width, height) for im in imgs]
         # A size that is not a multiple of the VAE stride: `VaeImageProcessor.preprocess` (lcm_controlnet.py:457, 230) rounds it
         # DOWN to a multiple of 8 with a Lanczos resize and the pipeline returns that size.  (There the control image is the
@@ -418,15 +431,38 @@ class VideoSDPipeline:
             eng._ref_epoch = self._ref_epoch
         np.random.seed(seed)  # kept for parity with videopipeline.py:112 (nothing downstream consumes it)
         t0 = time.perf_counter()
-        if raw is not None:
+        if i420 is not None:
+            eng.submit_raw_i420(i420[0] if len(i420) == 1 else i420, overlap=self._overlap_now(lane))
+            up = eng.last_upload_bytes
+        elif raw is not None:
             eng.submit_raw_u8(raw[0] if len(raw) == 1 else raw, overlap=self._overlap_now(lane))
+            up = sum((b[2] - b[0]) * (b[3] - b[1]) * 3 for b in (eng.ops.center_crop_box(f.shape[1], f.shape[0], width, height) for f in raw))
         else:
             frames = np.stack([np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8) for im in imgs])
             eng.submit_u8(frames[0] if len(imgs) == 1 else frames, overlap=self._overlap_now(lane))
+            up = frames.nbytes
+        self._io_bytes["up"] = up // len(imgs)  # bytes handed to the host-to-device copy per frame of this launch (counted, not timed)
         self._outstanding.append(eng)
         self._lanes_busy.append(int(lane))
         self._note("upload_enqueue", t0)
+        if any(yuv):  # (which results go back as I420, and whether the device converts them)
+            return (eng, len(imgs), yuv, i420 is not None)
         return (eng, len(imgs))
+
+    def _i420_on_device(self, frames, width: int, height: int, ref) -> bool:
+        """Do these `I420Frame`s take the device path (`Engine.submit_raw_i420` / `collect_i420`)?  Not what `_raw_frames` sends to the
+        host either: a target size that is not a multiple of 8, `ref=True` on an object that honours it, an ops object without the
+        kernels, a side above the limit.  Independent of `device_resize`: a new input type has no earlier behaviour to keep."""
+        from .lib import RESAMPLE_MAX_SIDE
+
+        ops = getattr(self.model, "ops", None)
+        if height % 8 or width % 8 or height <= 0 or width <= 0 or not all(hasattr(ops, a) for a in ("i420_to_rgb", "rgb_to_i420", "resample_rgb")):
+            return False
+        if bool(ref) and self.honor_ref_flag and not self.is_xl:
+            return False
+        if max(height, width) > RESAMPLE_MAX_SIDE:
+            return False
+        return all(max(f.size) <= RESAMPLE_MAX_SIDE for f in frames)
 
     def _raw_frames(self, imgs, width: int, height: int):
         """`device_resize`: the frames as uint8 [h][w][3] arrays for `Engine.submit_raw_u8`, or None when this call keeps the host
@@ -453,22 +489,33 @@ class VideoSDPipeline:
         return int(lane) < 2 and all(l < 2 for l in self._lanes_busy) and len(self._lanes_busy) < 2
 
     def collect_batch(self, handle):
-        eng, n = handle
+        eng, n = handle[:2]
+        yuv, on_device = (handle[2], handle[3]) if len(handle) > 2 else (None, False)
         t0 = time.perf_counter()
         try:
-            out = eng.collect_u8()
+            out = eng.collect_i420() if on_device else eng.collect_u8()
         finally:
             if eng in self._outstanding:
                 i = self._outstanding.index(eng)
                 self._outstanding.pop(i)
                 self._lanes_busy.pop(i)
         self._note("wait_download", t0)
+        self._io_bytes["down"] = (eng.last_download_bytes if on_device else out.nbytes) // n
         if getattr(eng, "last_gpu_ms", None) is not None:
             self._host_ms["gpu"].append(eng.last_gpu_ms)
+        if on_device:
+            t0 = time.perf_counter()
+            res = [out] if n == 1 else out
+            self._note("to_i420", t0)  # (the conversion ran on the device: nothing is left for the host)
+            return res
         out = out[None] if n == 1 else out
         t0 = time.perf_counter()
-        res = [Image.fromarray(o, mode="RGB") for o in out]
-        self._note("to_pil", t0)
+        if yuv is None:
+            res = [Image.fromarray(o, mode="RGB") for o in out]
+            self._note("to_pil", t0)
+            return res
+        res = [I420Frame.from_rgb(o) if k else Image.fromarray(o, mode="RGB") for o, k in zip(out, yuv)]
+        self._note("to_i420", t0)
         return res
 
     @property

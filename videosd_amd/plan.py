@@ -236,6 +236,25 @@ class CPlan:
         self.ctx.call("vsd_plan_infer_frame", self.h, frame.ctypes.data, h, w, 3 * w, out.ctypes.data)
         return out
 
+    def infer_frame_i420(self, frame):
+        """vsd_plan_infer_frame_i420: `frames.I420Frame` camera frame(s) of any size (a list of `batch` frames of one size) in, I420Frame(s)
+        of the plan's size out -- planes up, packed I420 down, converted on the device"""
+        from .frames import I420Frame
+
+        frames = [frame] if isinstance(frame, I420Frame) else list(frame)
+        if len(frames) != self.batch or not all(isinstance(f, I420Frame) and f.size == frames[0].size for f in frames):
+            raise ValueError(f"{self.batch} I420Frame(s) of one size")
+        w, h = frames[0].size
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        y = np.ascontiguousarray(np.stack([f.y for f in frames]))
+        u = np.ascontiguousarray(np.stack([f.u for f in frames]))
+        v = np.ascontiguousarray(np.stack([f.v for f in frames]))
+        one = self.H * self.W * 3 // 2
+        out = np.empty(self.batch * one, np.uint8)
+        self.ctx.call("vsd_plan_infer_frame_i420", self.h, y.ctypes.data, w, u.ctypes.data, v.ctypes.data, cw, h, w, out.ctypes.data)
+        res = [I420Frame(out[i * one:(i + 1) * one].copy(), self.W, self.H) for i in range(self.batch)]
+        return res[0] if self.batch == 1 else res
+
     def load_prompt(self, path: str):
         self.ctx.call("vsd_plan_load_prompt", self.h, path.encode())
 
