@@ -3,10 +3,12 @@
  * size / step count / prompt / frames per launch).
  *
  *   gcc -O2 examples/plan_host.c -Iinclude -Lvideosd_amd -lvsd -Wl,-rpath,$PWD/videosd_amd -o /tmp/plan_host
- *   /tmp/plan_host frame.vsdplan in.raw out.raw [launches] [lanes]
- * in.raw / out.raw: uint8 [frames per launch][H][W][3].  lanes (1..4): that many copies of the plan in flight, one per launch
+ *   /tmp/plan_host frame.vsdplan in.raw out.raw [launches] [lanes] [strength controlnet_scale]
+ * in.raw / out.raw: uint8 [frames per launch][H][W][3].  lanes (1..4): that many plans of the program in flight, one per launch
  * stream (the reference keeps N actors per node, server.py:132-137; inside one process the launch lanes do the same) -- frame k goes
- * to lane k mod lanes.  Prints the frame rate; out.raw is lane 0's last result.
+ * to lane k mod lanes.  The file is read ONCE: lane 0 loads it, the other lanes are clones that share its weights on the device
+ * (vsd_plan_clone_lane).  strength controlnet_scale: the reference's live options (server.py:163-197), applied to every lane with
+ * vsd_plan_set_options before the timed loop.  Prints the frame rate; out.raw is lane 0's last result.
  * (the reference's caller is a Python loop, server.py:104-143; this is that loop for a C / C++ / Go-via-cgo media server) */
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,7 +19,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    fprintf(stderr, "usage: %s plan in.raw out.raw [launches] [lanes]\n", argv[0]);
+    fprintf(stderr, "usage: %s plan in.raw out.raw [launches] [lanes] [strength controlnet_scale]\n", argv[0]);
     return 2;
   }
   const int launches = argc > 4 ? atoi(argv[4]) : 1;
@@ -30,9 +32,17 @@ int main(int argc, char** argv) {
   int dims[3];
   size_t n = 0;
   for (int l = 0; l < lanes; ++l) {
-    /* one lane: a stream of the plan's own; several: the process's launch streams (own hardware queues, vsd_stream_pool) */
-    const int rc = lanes == 1 ? vsd_plan_load(ctx, argv[1], &plan[l]) : vsd_plan_load_lane(ctx, argv[1], l, &plan[l]);
+    /* one lane: a stream of the plan's own; several: the process's launch streams (own hardware queues, vsd_stream_pool), lane 0 from
+     * the file and the others cloned from it */
+    const int rc = lanes == 1 ? vsd_plan_load(ctx, argv[1], &plan[l])
+                   : l == 0   ? vsd_plan_load_lane(ctx, argv[1], 0, &plan[0])
+                              : vsd_plan_clone_lane(ctx, plan[0], l, &plan[l]);
     if (rc != VSD_OK) { fprintf(stderr, "%s\n", vsd_last_error(ctx)); return 1; }
+    if (argc > 7) {
+      const int orc = vsd_plan_set_options(ctx, plan[l], atof(argv[6]), atof(argv[7]));
+      if (orc == VSD_PLAN_OTHER_PROGRAM) { fprintf(stderr, "strength %s needs another number of steps than this plan has: export another plan\n", argv[6]); return 1; }
+      if (orc != VSD_OK) { fprintf(stderr, "%s\n", vsd_last_error(ctx)); return 1; }
+    }
     vsd_plan_info(ctx, plan[l], dims);
     n = (size_t)dims[2] * dims[0] * dims[1] * 3;
     in[l] = vsd_pinned_alloc(ctx, n);

@@ -30,7 +30,8 @@ enum vsd_status {
   VSD_ERR_ARG = -1,      /* bad shape / unsupported configuration */
   VSD_ERR_HIP = -2,      /* a HIP runtime call failed */
   VSD_ERR_NOMEM = -3,
-  VSD_ERR_STATE = -4     /* call order (e.g. graph end without begin) */
+  VSD_ERR_STATE = -4,    /* call order (e.g. graph end without begin) */
+  VSD_PLAN_OTHER_PROGRAM = 1 /* no error: vsd_plan_set_options left the plan as it was, the options asked for need another program */
 };
 
 enum vsd_act { VSD_ACT_NONE = 0, VSD_ACT_RELU = 1, VSD_ACT_SILU = 2, VSD_ACT_GEGLU = 3, VSD_ACT_QUICKGELU = 4,
@@ -51,10 +52,10 @@ enum vsd_family {
   VSD_FAM_ATTENTION = 4, VSD_FAM_ELEMENTWISE = 5, VSD_FAM_COUNT = 6
 };
 
-/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame) and the size in
+/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
-#define VSD_VERSION 8
+#define VSD_VERSION 9
 int vsd_version(void);
 int vsd_conv_desc_size(void);
 
@@ -361,8 +362,9 @@ int vsd_pair_end(vsd_ctx* ctx, int* joined_out);
  * The reference's seam is a Python class (videopipeline.py:75-128) and the sequencing of a frame lives in videosd_amd/engine.py; for a
  * host without Python the engine's program is EXPORTED (videosd_amd/plan.py export_plan: every C-ABI call of the one-stream form with
  * its arguments, device pointers as (region, offset), the bytes of weights / constants / prompt block) and replayed here.
- * vsd_plan_load: allocate, upload, patch, replay under capture (one hipGraph); the plan is one (frame size, steps, strength, ControlNet
- * scale, prompt, frames per launch).  vsd_plan_infer: frame(s) uint8 [batch][H][W][3] on the HOST in, the same shape out; synchronous.
+ * vsd_plan_load: parse and check (argument tags of every call against this library's signatures, interface version and signature hash of
+ * a format 2 file -- all before anything is allocated), allocate, upload, patch, replay under capture (one hipGraph); the plan is one
+ * (frame size, steps, frames per launch); prompt, strength and ControlNet scale can be changed on the loaded plan (below).  vsd_plan_infer: frame(s) uint8 [batch][H][W][3] on the HOST in, the same shape out; synchronous.
  * The result is bit for bit the Python engine's.  vsd_plan_info: dims[0..2] = H, W, frames per launch. */
 typedef struct vsd_plan vsd_plan;
 int vsd_plan_load(vsd_ctx* ctx, const char* path, vsd_plan** plan_out);
@@ -393,6 +395,30 @@ int vsd_plan_infer_frame_i420(vsd_ctx* ctx, vsd_plan* plan, const void* y_host, 
                               int64_t uv_stride, int src_h, int src_w, void* out_i420_host);
 /* another prompt for a loaded plan: a file written by videosd_amd.plan.export_prompt (the prompt's constant block, same layout) */
 int vsd_plan_load_prompt(vsd_ctx* ctx, vsd_plan* plan, const char* path);
+/* LIVE OPTIONS (plan files of format 2).  The reference patches strength and controlnet_scale into the running stream on every
+ * data-channel message (server.py:163-197); the Python class follows with Engine.update_options.  A format 2 file carries what that
+ * needs, computed at export by the engine's own code: per network a 50-row table of the time-embedding projections (LCM timesteps take
+ * only the values 19, 39, ... 999), a table of the scheduler coefficients per timestep and the ControlNet residual scales' logspace.
+ * vsd_plan_set_options: ONE small launch on the plan's stream gathers the rows of the new schedule into the tables the captured graph
+ * reads and rewrites its constant block.  Stream-ordered: frames submitted before the call keep the old options, frames submitted
+ * after it get the new ones; no host synchronisation, no re-capture, the graph is not touched.  Returns VSD_OK, or
+ * VSD_PLAN_OTHER_PROGRAM -- not an error, nothing changed -- when `strength` gives another NUMBER of timesteps than the plan's program
+ * has or a timestep outside the table (Engine.update_options returning False: that is another plan).  An empty schedule and a format 1
+ * plan are errors with a reason.  The frames are bit for bit the Python engine's after update_options with the same values.
+ * vsd_lcm_timesteps: the schedule itself, on the host, no device and no context needed (videosd_amd/lcm.py lcm_timesteps in the same
+ * double arithmetic: 50 * strength truncated -- 0.58 gives 28 origin steps, not 29): out[0 .. *n) with *n <= steps, room for `steps`
+ * entries; VSD_ERR_ARG for steps < 1 or an empty schedule. */
+int vsd_lcm_timesteps(double strength, int steps, int* out, int* n);
+int vsd_plan_set_options(vsd_ctx* ctx, vsd_plan* plan, double strength, double controlnet_scale);
+/* LANES THAT SHARE WEIGHTS.  A second plan of the same program on launch stream `lane` (0..3, or -1 for a stream of its own) without
+ * reading the file again: the regions the exporter flagged as read-only network weights are SHARED with the source (reference-counted:
+ * freed with the last plan, whatever the order of vsd_plan_free); counters, constants, time tables, prompt block, frame buffers and
+ * scratch are the clone's own, copied device to device from the source after waiting for its stream -- the clone starts with the
+ * source's current prompt and options, and both are per plan afterwards.  A format 1 file flags nothing: its clone shares nothing.
+ * vsd_plan_memory: out[0] = bytes of the regions this plan owns, out[1] = bytes of the regions it may share with clones (the buffers
+ * that the camera-frame entry points grow on demand are not counted). */
+int vsd_plan_clone_lane(vsd_ctx* ctx, vsd_plan* plan, int lane, vsd_plan** plan_out);
+int vsd_plan_memory(vsd_ctx* ctx, vsd_plan* plan, uint64_t* out);
 void vsd_plan_free(vsd_ctx* ctx, vsd_plan* plan);
 /* page-locked host memory for a plan's frames (NULL on failure) */
 void* vsd_pinned_alloc(vsd_ctx* ctx, size_t bytes);

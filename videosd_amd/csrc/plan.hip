@@ -2,18 +2,26 @@
 //
 // SURVEY.md section 8b sketched whole-frame C entry points; a frame's sequencing lives in engine.py, so what a non-Python host gets
 // is the RECORDED program: every C-ABI call of the engine's one-stream form with its arguments, device pointers as (region, offset).
-// vsd_plan_load allocates the regions, uploads the saved ones (weights, constants, prompt block, counters), patches the pointers,
-// replays the calls under stream capture and instantiates the graph; vsd_plan_infer = upload the frame(s), one graph launch,
-// download.  Same kernels with the same arguments as the Python engine: the same bits (tests/test_plan_gpu.py).
+// vsd_plan_load PARSES the file into a PlanProgram and checks it (argument tags against this library's signatures, interface version
+// and signature hash of a format 2 file, every offset against its region) before anything is allocated; then it allocates the regions,
+// uploads the saved ones (weights, constants, prompt block, counters), and BINDS: patches the pointers, replays the calls once eagerly
+// and once under stream capture, instantiates the graph.  vsd_plan_infer = upload the frame(s), one graph launch, download.  Same
+// kernels with the same arguments as the Python engine: the same bits (tests/test_plan_gpu.py).
+// vsd_plan_clone_lane binds the same PlanProgram to a second set of regions: the ones flagged as read-only weights are the source's
+// (reference-counted), the rest are the clone's own.  vsd_plan_set_options: csrc/plan_options.hip.
 #include <stdarg.h>
+#include <math.h>
 #include <algorithm>
+#include <memory>
 
 #include "common.h"
+#include "plan_options.h"
 
 namespace {
 
 enum { T_I32 = 0, T_F32 = 1, T_PTR = 2, T_NULL = 3, T_STREAM = 4, T_DESC = 5 };
 constexpr int PLAN_MAX_ARGS = 24;
+constexpr uint32_t REGION_SHARED = 1;  // region flag, bit 0: read-only network weights, shareable between lanes
 
 union PlanArg {
   void* p;
@@ -26,12 +34,71 @@ struct PlanCall {
   PlanArg a[PLAN_MAX_ARGS];
 };
 
+// per entry point "name:tags" (scripts/gen_plan_dispatch.py): what a recorded call must look like
+const char* const PLAN_SIGS[] = {
+#define PLAN_DISPATCH_TAGS
+#include "plan_dispatch.inc"
+#undef PLAN_DISPATCH_TAGS
+};
+constexpr int PLAN_NFUNCS = (int)(sizeof(PLAN_SIGS) / sizeof(PLAN_SIGS[0]));
+
+const char* plan_tags(int fn) { return strchr(PLAN_SIGS[fn], ':') + 1; }
+
+uint64_t plan_signature_hash() {  // FNV-1a over the lines, each followed by a newline (videosd_amd/plan.py signature_hash)
+  uint64_t h = 0xCBF29CE484222325ull;
+  for (int i = 0; i < PLAN_NFUNCS; ++i)
+    for (const char* c = PLAN_SIGS[i];; ++c) {
+      h = (h ^ (unsigned char)(*c ? *c : '\n')) * 0x100000001B3ull;
+      if (!*c) break;
+    }
+  return h;
+}
+
+// ---- the file as parsed: what every plan of this program shares on the host
+struct RawArg {
+  uint32_t tag, aux;  // (T_DESC: aux = index into `blobs`)
+  uint64_t val;
+};
+struct RawCall {
+  int fn, n;
+  RawArg a[PLAN_MAX_ARGS];
+};
+struct RawFix {
+  uint32_t boff, reg;
+  uint64_t off;
+};
+struct RawBlob {
+  std::vector<unsigned char> bytes;
+  std::vector<RawFix> fix;
+};
+struct RawOptTable {
+  uint32_t table_r, live_r;
+  uint64_t table_off, live_off, live_stride, row_bytes;
+};
+struct PlanProgram {
+  uint32_t version = 0;
+  int H = 0, W = 0, batch = 0;
+  std::vector<uint64_t> size;
+  std::vector<uint32_t> saved, flags;
+  uint32_t in_r = 0, out_r = 0, pr_r = 0;
+  uint64_t in_off = 0, out_off = 0, pr_off = 0, pr_bytes = 0;
+  std::vector<RawCall> calls;
+  std::vector<RawBlob> blobs;
+  // the options section (format 2)
+  bool options = false;
+  uint32_t n = 0, steps = 0, nres = 0;
+  uint32_t consts_r = 0, coef_r = 0;
+  uint64_t consts_off = 0, coef_off = 0;
+  std::vector<RawOptTable> tabs;
+};
+
 }  // namespace
 
 struct vsd_plan {
   vsd_ctx* ctx = nullptr;
   int H = 0, W = 0, batch = 0;
-  std::vector<void*> regions;
+  std::shared_ptr<const PlanProgram> prog;
+  std::vector<std::shared_ptr<void>> regions;     // (a region flagged REGION_SHARED may belong to several plans: freed with the last)
   std::vector<std::vector<unsigned char>> blobs;  // descriptor arrays of the calls (the calls point into them: a moved vector keeps its buffer)
   std::vector<PlanCall> calls;
   hipStream_t stream = nullptr;
@@ -76,11 +143,226 @@ void plan_release(vsd_plan* p) {
   if (!p) return;
   if (p->graph) (void)hipGraphExecDestroy((hipGraphExec_t)p->graph);
   if (p->stream && p->own_stream) (void)hipStreamDestroy(p->stream);
-  for (void* r : p->regions)
-    if (r) (void)hipFree(r);
+  p->regions.clear();
   for (void* r : {p->raw, p->work, p->table_x, p->table_y, p->yuv_in, p->yuv_out})
     if (r) (void)hipFree(r);
   delete p;
+}
+
+std::shared_ptr<void> region_alloc(uint64_t bytes) {
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes ? bytes : 16) != hipSuccess) return nullptr;
+  return std::shared_ptr<void>(d, [](void* q) { (void)hipFree(q); });
+}
+
+// [off, off + bytes) inside region `reg`
+bool plan_inside(const PlanProgram& g, uint32_t reg, uint64_t off, uint64_t bytes) {
+  return reg < g.size.size() && off <= g.size[reg] && bytes <= g.size[reg] - off;
+}
+
+// Parse and check a plan file up to the bytes of its regions (`f` is left there).  Nothing here touches the device.
+const char* plan_parse(FILE* f, PlanProgram& g) {
+  Reader r{f};
+  g.version = r.get<uint32_t>();
+  g.H = (int)r.get<uint32_t>();
+  g.W = (int)r.get<uint32_t>();
+  g.batch = (int)r.get<uint32_t>();
+  const uint32_t nreg = r.get<uint32_t>(), ncall = r.get<uint32_t>();
+  g.in_r = r.get<uint32_t>();
+  g.in_off = r.get<uint64_t>();
+  g.out_r = r.get<uint32_t>();
+  g.out_off = r.get<uint64_t>();
+  g.pr_r = r.get<uint32_t>();
+  g.pr_off = r.get<uint64_t>();
+  g.pr_bytes = r.get<uint64_t>();
+  if (!r.ok || (g.version != 1 && g.version != 2) || nreg == 0 || nreg > (1u << 20) || ncall == 0 || ncall > (1u << 22) || g.in_r >= nreg || g.out_r >= nreg ||
+      g.H < 1 || g.W < 1 || g.batch < 1 || g.H > (1 << 16) || g.W > (1 << 16) || g.batch > (1 << 10))
+    return "bad header";
+  uint32_t ntab = 0;
+  if (g.version >= 2) {
+    const uint32_t ext = r.get<uint32_t>(), iface = r.get<uint32_t>();
+    const uint64_t hash = r.get<uint64_t>();
+    if (!r.ok) return "truncated extension";
+    if (iface != VSD_VERSION) return "written for another interface version of the library: export the plan again";
+    if (hash != plan_signature_hash()) return "written against other entry point signatures: export the plan again";
+    g.n = r.get<uint32_t>();
+    g.steps = r.get<uint32_t>();
+    g.nres = r.get<uint32_t>();
+    ntab = r.get<uint32_t>();
+    (void)r.get<double>();  // strength and ControlNet scale as exported: the live constants hold them already
+    (void)r.get<double>();
+    g.consts_r = r.get<uint32_t>();
+    g.coef_r = r.get<uint32_t>();
+    g.consts_off = r.get<uint64_t>();
+    g.coef_off = r.get<uint64_t>();
+    if (!r.ok) return "truncated options section";
+    if (g.n < 1 || g.n > (uint32_t)PLAN_OPT_ROWS || g.steps < g.n || g.steps > 1000 || g.nres < 1 || g.nres > 64 || ntab < 1 || ntab > (uint32_t)PLAN_OPT_TABLES || ext != 12 + 56 + 40 * ntab)
+      return "bad options section";
+    g.tabs.resize(ntab);
+    for (RawOptTable& t : g.tabs) {
+      t.table_r = r.get<uint32_t>();
+      t.live_r = r.get<uint32_t>();
+      t.table_off = r.get<uint64_t>();
+      t.live_off = r.get<uint64_t>();
+      t.live_stride = r.get<uint64_t>();
+      t.row_bytes = r.get<uint64_t>();
+    }
+    if (!r.ok) return "truncated options section";
+    g.options = true;
+  }
+  g.size.resize(nreg);
+  g.saved.resize(nreg);
+  g.flags.resize(nreg);
+  for (uint32_t i = 0; i < nreg; ++i) {
+    g.size[i] = r.get<uint64_t>();
+    g.saved[i] = r.get<uint32_t>();
+    g.flags[i] = g.version >= 2 ? r.get<uint32_t>() : ((void)r.get<uint32_t>(), 0u);
+    if (r.ok && (g.size[i] > (1ull << 40) || ((g.flags[i] & REGION_SHARED) && !g.saved[i]))) return "bad region table";
+  }
+  if (!r.ok) return "truncated region table";
+  if (g.options) {
+    // what vsd_plan_set_options reads and writes, checked once: inside saved regions, dword-aligned, and never in a shared region
+    auto rw = [&](uint32_t reg, uint64_t off, uint64_t bytes, bool written) {
+      return plan_inside(g, reg, off, bytes) && off % 4 == 0 && g.saved[reg] && !(written && (g.flags[reg] & REGION_SHARED));
+    };
+    if (!rw(g.consts_r, g.consts_off, 4ull * (2 + PLAN_OPT_COEF * g.n + g.nres), true) ||
+        !rw(g.coef_r, g.coef_off, 4ull * (PLAN_OPT_ROWS * PLAN_OPT_COEF + g.nres), false))
+      return "option constants outside their regions";
+    for (const RawOptTable& t : g.tabs)
+      if (t.row_bytes == 0 || t.row_bytes % 4 || t.live_stride % 4 || t.live_stride < t.row_bytes || t.row_bytes > (1ull << 30) || t.live_stride > (1ull << 30) ||
+          !rw(t.table_r, t.table_off, t.row_bytes * PLAN_OPT_ROWS, false) || !rw(t.live_r, t.live_off, t.live_stride * (g.n - 1) + t.row_bytes, true))
+        return "option tables outside their regions";
+  }
+  g.calls.resize(ncall);
+  for (uint32_t c = 0; c < ncall; ++c) {
+    RawCall& rc = g.calls[c];
+    rc.fn = (int)r.get<uint32_t>();
+    rc.n = (int)r.get<uint32_t>();
+    if (!r.ok || rc.fn < 0 || rc.fn >= PLAN_NFUNCS || rc.n < 0 || rc.n > PLAN_MAX_ARGS) return "bad call record";
+    const char* tags = plan_tags(rc.fn);
+    if ((size_t)rc.n != strlen(tags)) return "a call with another number of arguments than its entry point takes";
+    int desc_count = -1, desc_at = -1;
+    for (int k = 0; k < rc.n; ++k) {
+      RawArg& a = rc.a[k];
+      a.tag = r.get<uint32_t>();
+      a.aux = r.get<uint32_t>();
+      a.val = r.get<uint64_t>();
+      if (!r.ok) return "truncated call list";
+      // the tag against the entry point's signature: an integer where a pointer is expected never reaches the call
+      bool fits = false;
+      switch (tags[k]) {
+        case 'i': fits = a.tag == T_I32; break;
+        case 'f': fits = a.tag == T_F32; break;
+        case 'p': fits = a.tag == T_PTR || a.tag == T_STREAM || a.tag == T_NULL; break;  // (a pointer may be optional: the entry point says)
+        case 'd': fits = a.tag == T_DESC; break;
+        case 'o': fits = a.tag == T_NULL; break;
+      }
+      if (a.tag > T_DESC) return "unknown argument tag";
+      if (!fits) return "an argument tag that does not fit its entry point's signature";
+      if (a.tag == T_PTR && !plan_inside(g, a.aux, a.val, 1)) return "pointer outside its region";
+      if (a.tag == T_DESC) {
+        if (a.aux == 0 || a.aux > VSD_CONV_GROUP_MAX || a.val != (uint64_t)a.aux * sizeof(vsd_conv_desc)) return "descriptor array of another interface version";
+        RawBlob blob;
+        blob.bytes.resize((size_t)a.val);
+        r.bytes(blob.bytes.data(), blob.bytes.size());
+        const uint32_t nfix = r.get<uint32_t>();
+        if (!r.ok || nfix > 64 * a.aux) return "bad descriptor record";
+        blob.fix.resize(nfix);
+        for (RawFix& x : blob.fix) {
+          x.boff = r.get<uint32_t>();
+          x.reg = r.get<uint32_t>();
+          x.off = r.get<uint64_t>();
+          if (!r.ok || (uint64_t)x.boff + sizeof(void*) > blob.bytes.size() || !plan_inside(g, x.reg, x.off, 1)) return "bad descriptor pointer";
+        }
+        desc_count = (int)a.aux;
+        desc_at = k;
+        a.aux = (uint32_t)g.blobs.size();
+        g.blobs.push_back(std::move(blob));
+      }
+    }
+    // a descriptor array is followed by its count (vsd_conv_gemm_group) or is one descriptor (vsd_conv_gemm)
+    if (desc_at >= 0) {
+      const bool counted = desc_at + 1 < rc.n && tags[desc_at + 1] == 'i';
+      if (counted ? (int)(int64_t)rc.a[desc_at + 1].val != desc_count : desc_count != 1) return "a descriptor array of another length than its call says";
+    }
+  }
+  if (!plan_inside(g, g.in_r, g.in_off, (uint64_t)g.batch * g.H * g.W * 3) || !plan_inside(g, g.out_r, g.out_off, (uint64_t)g.batch * g.H * g.W * 3) ||
+      !plan_inside(g, g.pr_r, g.pr_off, g.pr_bytes) || g.in_off >= g.size[g.in_r] || g.out_off >= g.size[g.out_r] || g.pr_off >= g.size[g.pr_r])
+    return "frame buffers / prompt block outside their regions";
+  return nullptr;
+}
+
+// The plan's regions are in place: patch the program's pointers into this plan's calls and descriptor arrays, then one eager pass
+// (first-touch of every kernel, the error reports of the ops) and the captured one.  On failure the caller releases the plan.
+int plan_bind(vsd_ctx* ctx, vsd_plan* p, const char* who) {
+  const PlanProgram& g = *p->prog;
+  auto at = [&](uint32_t reg, uint64_t off) { return (void*)((char*)p->regions[reg].get() + off); };
+  p->H = g.H; p->W = g.W; p->batch = g.batch;
+  p->blobs.resize(g.blobs.size());
+  for (size_t b = 0; b < g.blobs.size(); ++b) {
+    p->blobs[b] = g.blobs[b].bytes;
+    for (const RawFix& x : g.blobs[b].fix) {
+      void* q = at(x.reg, x.off);
+      memcpy(p->blobs[b].data() + x.boff, &q, sizeof(void*));
+    }
+  }
+  p->calls.resize(g.calls.size());
+  for (size_t c = 0; c < g.calls.size(); ++c) {
+    const RawCall& rc = g.calls[c];
+    PlanCall& pc = p->calls[c];
+    pc.fn = rc.fn;
+    pc.n = rc.n;
+    for (int k = 0; k < rc.n; ++k) {
+      const RawArg& a = rc.a[k];
+      pc.a[k].p = nullptr;
+      switch (a.tag) {
+        case T_I32: pc.a[k].i = (int)(int64_t)a.val; break;
+        case T_F32: { const uint32_t b = (uint32_t)a.val; memcpy(&pc.a[k].f, &b, 4); break; }
+        case T_PTR: pc.a[k].p = at(a.aux, a.val); break;
+        case T_STREAM: pc.a[k].p = (void*)p->stream; break;
+        case T_DESC: pc.a[k].p = p->blobs[a.aux].data(); break;
+        default: break;
+      }
+    }
+  }
+  p->in = at(g.in_r, g.in_off);
+  p->out = at(g.out_r, g.out_off);
+  p->prompt = at(g.pr_r, g.pr_off);
+  p->prompt_bytes = (size_t)g.pr_bytes;
+  p->io_bytes = (size_t)p->batch * p->H * p->W * 3;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1) {
+      int rc = vsd_graph_begin(ctx, (void*)p->stream);
+      if (rc != VSD_OK) return rc;
+    }
+    int rc = VSD_OK;
+    for (const PlanCall& pc : p->calls) {
+      rc = plan_dispatch(ctx, pc.fn, pc.n, pc.a);
+      if (rc != VSD_OK) break;
+    }
+    if (pass == 1) {
+      const int rc2 = vsd_graph_end(ctx, (void*)p->stream, &p->graph);
+      if (rc == VSD_OK) rc = rc2;
+    }
+    if (rc != VSD_OK) {
+      std::string why = ctx->err;
+      return vsd_fail(ctx, rc < 0 && rc > -1000 && why.empty() ? VSD_ERR_ARG : rc, "%s: replaying the program failed (%d): %s", who, rc, why.c_str());
+    }
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return vsd_fail(ctx, VSD_ERR_HIP, "%s: the eager pass faulted", who);
+  }
+  return VSD_OK;
+}
+
+// the plan's launch stream: lane >= 0: launch stream `lane` of the process's pool, else one of the plan's own
+bool plan_stream(vsd_ctx* ctx, vsd_plan* p, int lane) {
+  if (lane >= 0) {
+    void* pool[VSD_POOL_STREAMS];
+    if (vsd_stream_pool(ctx, pool) != VSD_OK) return false;
+    p->stream = (hipStream_t)pool[lane];
+    p->own_stream = false;
+    return true;
+  }
+  return hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) == hipSuccess;
 }
 
 // a device buffer of the plan grown to `need` bytes (never shrunk); waits for the plan's stream first: nothing in flight reads the old one
@@ -120,141 +402,154 @@ extern "C" int vsd_plan_load_lane(vsd_ctx* ctx, const char* path, int lane, vsd_
   *plan_out = nullptr;
   FILE* f = fopen(path, "rb");
   if (!f) return vsd_fail(ctx, VSD_ERR_ARG, "plan_load: cannot open %s", path);
-  Reader r{f};
   char magic[8];
-  r.bytes(magic, 8);
-  if (!r.ok || memcmp(magic, "VSDPLAN1", 8) != 0) {
+  if (fread(magic, 1, 8, f) != 8 || memcmp(magic, "VSDPLAN1", 8) != 0) {
     fclose(f);
     return vsd_fail(ctx, VSD_ERR_ARG, "plan_load: %s is not a plan file", path);
   }
-  const uint32_t version = r.get<uint32_t>();
-  vsd_plan* p = new vsd_plan;
-  p->ctx = ctx;
-  p->H = (int)r.get<uint32_t>();
-  p->W = (int)r.get<uint32_t>();
-  p->batch = (int)r.get<uint32_t>();
-  const uint32_t nreg = r.get<uint32_t>(), ncall = r.get<uint32_t>();
-  const uint32_t in_r = r.get<uint32_t>();
-  const uint64_t in_off = r.get<uint64_t>();
-  const uint32_t out_r = r.get<uint32_t>();
-  const uint64_t out_off = r.get<uint64_t>();
-  const uint32_t pr_r = r.get<uint32_t>();
-  const uint64_t pr_off = r.get<uint64_t>(), pr_bytes = r.get<uint64_t>();
+  vsd_plan* p = nullptr;
   auto fail = [&](const char* what) {
     fclose(f);
     plan_release(p);
     return vsd_fail(ctx, VSD_ERR_ARG, "plan_load: %s (%s)", what, path);
   };
-  if (!r.ok || version != 1 || nreg == 0 || nreg > (1u << 20) || ncall == 0 || ncall > (1u << 22) || in_r >= nreg || out_r >= nreg)
-    return fail("bad header");
-  std::vector<uint64_t> size(nreg);
-  std::vector<uint32_t> saved(nreg);
-  for (uint32_t i = 0; i < nreg; ++i) {
-    size[i] = r.get<uint64_t>();
-    saved[i] = r.get<uint32_t>();
-    (void)r.get<uint32_t>();
+  auto prog = std::make_shared<PlanProgram>();
+  if (const char* why = plan_parse(f, *prog)) return fail(why);
+  // the bytes of the saved regions must all be there before the first allocation: a cut file costs nothing
+  {
+    uint64_t need = 0;
+    for (size_t i = 0; i < prog->size.size(); ++i)
+      if (prog->saved[i]) need += prog->size[i];
+    const long here = ftell(f);
+    if (here < 0 || fseek(f, 0, SEEK_END) != 0) return fail("cannot seek");
+    const long total = ftell(f);
+    if (total < 0 || (uint64_t)(total - here) < need) return fail("truncated region contents");
+    if (fseek(f, here, SEEK_SET) != 0) return fail("cannot seek");
   }
-  if (!r.ok) return fail("truncated region table");
+  const PlanProgram& g = *prog;
+  const size_t nreg = g.size.size();
+  p = new vsd_plan;
+  p->ctx = ctx;
+  p->prog = prog;
   (void)hipSetDevice(ctx->device);
+  if (!plan_stream(ctx, p, lane)) return fail("no launch stream");
   p->regions.assign(nreg, nullptr);
-  for (uint32_t i = 0; i < nreg; ++i) {
-    if (hipMalloc(&p->regions[i], size[i] ? size[i] : 16) != hipSuccess) return fail("out of device memory");
-    if (!saved[i] && hipMemset(p->regions[i], 0, size[i]) != hipSuccess) return fail("hipMemset failed");
+  for (size_t i = 0; i < nreg; ++i) {
+    if (!(p->regions[i] = region_alloc(g.size[i]))) return fail("out of device memory");
+    if (!g.saved[i] && hipMemsetAsync(p->regions[i].get(), 0, g.size[i], p->stream) != hipSuccess) return fail("hipMemset failed");
   }
-  if (lane >= 0) {
-    void* pool[VSD_POOL_STREAMS];
-    if (vsd_stream_pool(ctx, pool) != VSD_OK) return fail("no launch stream pool");
-    p->stream = (hipStream_t)pool[lane];
-    p->own_stream = false;
-  } else if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) {
-    return fail("hipStreamCreate failed");
-  }
-  auto at = [&](uint32_t reg, uint64_t off, void** out) {
-    if (reg >= nreg || off >= size[reg]) return false;
-    *out = (char*)p->regions[reg] + off;
-    return true;
-  };
-  p->calls.resize(ncall);
-  for (uint32_t c = 0; c < ncall; ++c) {
-    PlanCall& pc = p->calls[c];
-    pc.fn = (int)r.get<uint32_t>();
-    pc.n = (int)r.get<uint32_t>();
-    if (!r.ok || pc.n < 0 || pc.n > PLAN_MAX_ARGS) return fail("bad call record");
-    for (int k = 0; k < pc.n; ++k) {
-      const uint32_t tag = r.get<uint32_t>(), aux = r.get<uint32_t>();
-      const uint64_t val = r.get<uint64_t>();
-      if (!r.ok) return fail("truncated call list");
-      pc.a[k].p = nullptr;
-      switch (tag) {
-        case T_I32: pc.a[k].i = (int)(int64_t)val; break;
-        case T_F32: { const uint32_t b = (uint32_t)val; memcpy(&pc.a[k].f, &b, 4); break; }
-        case T_PTR: if (!at(aux, val, &pc.a[k].p)) return fail("pointer outside its region"); break;
-        case T_NULL: break;
-        case T_STREAM: pc.a[k].p = (void*)p->stream; break;
-        case T_DESC: {
-          if (aux == 0 || aux > VSD_CONV_GROUP_MAX || val != (uint64_t)aux * sizeof(vsd_conv_desc)) return fail("descriptor array of another interface version");
-          p->blobs.emplace_back((size_t)val);
-          std::vector<unsigned char>& blob = p->blobs.back();
-          r.bytes(blob.data(), blob.size());
-          const uint32_t nfix = r.get<uint32_t>();
-          if (!r.ok || nfix > 64 * aux) return fail("bad descriptor record");
-          for (uint32_t j = 0; j < nfix; ++j) {
-            const uint32_t boff = r.get<uint32_t>(), reg = r.get<uint32_t>();
-            const uint64_t off = r.get<uint64_t>();
-            void* q = nullptr;
-            if (!r.ok || boff + sizeof(void*) > blob.size() || !at(reg, off, &q)) return fail("bad descriptor pointer");
-            memcpy(blob.data() + boff, &q, sizeof(void*));
-          }
-          pc.a[k].p = blob.data();
-          break;
-        }
-        default: return fail("unknown argument tag");
-      }
-    }
-  }
-  for (uint32_t i = 0; i < nreg; ++i) {
-    if (!saved[i]) continue;
+  {
     std::vector<unsigned char> host(1 << 24);
-    uint64_t done = 0;
-    while (done < size[i]) {
-      const size_t n = (size_t)std::min<uint64_t>(host.size(), size[i] - done);
-      if (!r.bytes(host.data(), n)) return fail("truncated region contents");
-      if (hipMemcpy((char*)p->regions[i] + done, host.data(), n, hipMemcpyHostToDevice) != hipSuccess) return fail("upload failed");
-      done += n;
+    for (size_t i = 0; i < nreg; ++i) {
+      if (!g.saved[i]) continue;
+      uint64_t done = 0;
+      while (done < g.size[i]) {
+        const size_t n = (size_t)std::min<uint64_t>(host.size(), g.size[i] - done);
+        if (fread(host.data(), 1, n, f) != n) return fail("truncated region contents");
+        if (hipMemcpy((char*)p->regions[i].get() + done, host.data(), n, hipMemcpyHostToDevice) != hipSuccess) return fail("upload failed");
+        done += n;
+      }
     }
   }
   fclose(f);
   f = nullptr;
-  if (!at(in_r, in_off, &p->in) || !at(out_r, out_off, &p->out) || !at(pr_r, pr_off, &p->prompt) || pr_off + pr_bytes > size[pr_r]) {
+  const int rc = plan_bind(ctx, p, "plan_load");
+  if (rc != VSD_OK) {
     plan_release(p);
-    return vsd_fail(ctx, VSD_ERR_ARG, "plan_load: frame buffers / prompt block outside their regions");
-  }
-  p->prompt_bytes = (size_t)pr_bytes;
-  p->io_bytes = (size_t)p->batch * p->H * p->W * 3;
-  // one eager pass (first-touch of every kernel, the error reports of the ops), then the captured one
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1) {
-      int rc = vsd_graph_begin(ctx, (void*)p->stream);
-      if (rc != VSD_OK) { plan_release(p); return rc; }
-    }
-    int rc = VSD_OK;
-    for (const PlanCall& pc : p->calls) {
-      rc = plan_dispatch(ctx, pc.fn, pc.n, pc.a);
-      if (rc != VSD_OK) break;
-    }
-    if (pass == 1) {
-      const int rc2 = vsd_graph_end(ctx, (void*)p->stream, &p->graph);
-      if (rc == VSD_OK) rc = rc2;
-    }
-    if (rc != VSD_OK) {
-      std::string why = ctx->err;
-      plan_release(p);
-      return vsd_fail(ctx, rc < 0 && rc > -1000 && why.empty() ? VSD_ERR_ARG : rc, "plan_load: replaying the program failed (%d): %s", rc, why.c_str());
-    }
-    if (hipStreamSynchronize(p->stream) != hipSuccess) { plan_release(p); return vsd_fail(ctx, VSD_ERR_HIP, "plan_load: the eager pass faulted"); }
+    return rc;
   }
   *plan_out = p;
   return VSD_OK;
+}
+
+// A second plan of the same program that shares the source's read-only weights (include/vsd.h).
+extern "C" int vsd_plan_clone_lane(vsd_ctx* ctx, vsd_plan* src, int lane, vsd_plan** plan_out) {
+  if (!ctx || !src || !plan_out) return VSD_ERR_ARG;
+  if (lane >= VSD_POOL_STREAMS) return vsd_fail(ctx, VSD_ERR_ARG, "plan_clone_lane: lane %d (0..%d, or -1 for a stream of the plan's own)", lane, VSD_POOL_STREAMS - 1);
+  *plan_out = nullptr;
+  (void)hipSetDevice(ctx->device);
+  VSD_HIP(ctx, hipStreamSynchronize(src->stream));  // what the clone copies is what the source's last frame left
+  const PlanProgram& g = *src->prog;
+  vsd_plan* p = new vsd_plan;
+  p->ctx = ctx;
+  p->prog = src->prog;
+  auto fail = [&](int code, const char* what) {
+    plan_release(p);
+    return vsd_fail(ctx, code, "plan_clone_lane: %s", what);
+  };
+  if (!plan_stream(ctx, p, lane)) return fail(VSD_ERR_HIP, "no launch stream");
+  const size_t nreg = g.size.size();
+  p->regions.assign(nreg, nullptr);
+  for (size_t i = 0; i < nreg; ++i) {
+    if (g.flags[i] & REGION_SHARED) {
+      p->regions[i] = src->regions[i];
+      continue;
+    }
+    if (!(p->regions[i] = region_alloc(g.size[i]))) return fail(VSD_ERR_NOMEM, "out of device memory");
+    const hipError_t e = g.saved[i] ? hipMemcpyAsync(p->regions[i].get(), src->regions[i].get(), g.size[i], hipMemcpyDeviceToDevice, p->stream)
+                                    : hipMemsetAsync(p->regions[i].get(), 0, g.size[i], p->stream);
+    if (e != hipSuccess) return fail(VSD_ERR_HIP, "copying the source's regions failed");
+  }
+  const int rc = plan_bind(ctx, p, "plan_clone_lane");
+  if (rc != VSD_OK) {
+    plan_release(p);
+    return rc;
+  }
+  *plan_out = p;
+  return VSD_OK;
+}
+
+extern "C" int vsd_plan_memory(vsd_ctx* ctx, vsd_plan* plan, uint64_t* out) {
+  if (!ctx || !plan || !out) return VSD_ERR_ARG;
+  const PlanProgram& g = *plan->prog;
+  out[0] = out[1] = 0;
+  for (size_t i = 0; i < g.size.size(); ++i) out[(g.flags[i] & REGION_SHARED) ? 1 : 0] += g.size[i];
+  return VSD_OK;
+}
+
+// lcm.lcm_timesteps (videosd_amd/lcm.py) on the host, in the same double arithmetic: 50 * strength truncated towards zero
+extern "C" int vsd_lcm_timesteps(double strength, int steps, int* out, int* n) {
+  if (!out || !n) return VSD_ERR_ARG;
+  *n = 0;
+  if (steps < 1 || !(strength == strength) || strength > 1e6 || strength < -1e6) return VSD_ERR_ARG;
+  const int origin = (int)(50.0 * strength);  // origin timesteps 19, 39, ...: index j holds 20 (j + 1) - 1
+  if (origin < 1) return VSD_ERR_ARG;         // an empty schedule
+  const int skipping = std::max(origin / steps, 1);
+  int count = 0;
+  for (int j = origin - 1; j >= 0 && count < steps; j -= skipping) out[count++] = 20 * (j + 1) - 1;
+  *n = count;
+  return VSD_OK;
+}
+
+// Engine.update_options for a loaded plan: include/vsd.h; the launch: csrc/plan_options.hip
+extern "C" int vsd_plan_set_options(vsd_ctx* ctx, vsd_plan* plan, double strength, double controlnet_scale) {
+  if (!ctx || !plan) return VSD_ERR_ARG;
+  const PlanProgram& g = *plan->prog;
+  if (!g.options)
+    return vsd_fail(ctx, VSD_ERR_ARG, "plan_set_options: the plan file has format version %u, which holds no option tables: export the plan again", g.version);
+  std::vector<int> ts(g.steps);
+  int n = 0;
+  if (vsd_lcm_timesteps(strength, (int)g.steps, ts.data(), &n) != VSD_OK)
+    return vsd_fail(ctx, VSD_ERR_ARG, "plan_set_options: strength %g gives an empty LCM schedule", strength);
+  if (n != (int)g.n) return VSD_PLAN_OTHER_PROGRAM;
+  PlanOptArgs a{};
+  for (int i = 0; i < n; ++i) {
+    const int row = (ts[i] + 1) / 20 - 1;
+    if ((ts[i] + 1) % 20 != 0 || row < 0 || row >= PLAN_OPT_ROWS) return VSD_PLAN_OTHER_PROGRAM;
+    a.row[i] = (unsigned char)row;
+  }
+  auto at = [&](uint32_t reg, uint64_t off) { return (void*)((char*)plan->regions[reg].get() + off); };
+  a.n = n;
+  a.nres = (int)g.nres;
+  a.ntab = (int)g.tabs.size();
+  a.scale = (float)controlnet_scale;
+  a.coef = (const float*)at(g.coef_r, g.coef_off);
+  a.consts = (float*)at(g.consts_r, g.consts_off);
+  for (int t = 0; t < a.ntab; ++t) {
+    const RawOptTable& r = g.tabs[t];
+    a.tab[t] = {(const uint32_t*)at(r.table_r, r.table_off), (uint32_t*)at(r.live_r, r.live_off), (uint32_t)(r.row_bytes / 4), (uint32_t)(r.live_stride / 4)};
+  }
+  return plan_options_launch(ctx, plan->stream, a);
 }
 
 extern "C" int vsd_plan_info(vsd_ctx* ctx, vsd_plan* plan, int* dims) {

@@ -652,7 +652,8 @@ class VideoSDPipeline:
         """The program `infer(img, **options)` runs on this pipeline -- model, prompt, frame size, steps, strength, ControlNet scale --
         as a FILE for hosts without Python: include/vsd.h vsd_plan_load / vsd_plan_infer (examples/plan_host.c) replay it with the
         same kernels and arguments, bit for bit this class's frames.  The host feeds frames already cropped / resized to
-        (height, width) (videopipeline.py:92-107 does that with PIL); another size, prompt or step count is another plan.
+        (height, width) (videopipeline.py:92-107 does that with PIL); another size or step count is another plan, another prompt is
+        `export_prompt`, another strength / ControlNet scale is vsd_plan_set_options on the loaded plan.
         `frames_per_launch` > 1: the coalesced program of `infer_batch`.  Returns the exporter's summary (videosd_amd/plan.py)."""
         from .plan import export_plan
 

@@ -7,15 +7,38 @@ that without a second engine: `export_plan(engine, path)` runs the engine's one-
 of the process (weights, per-plan constants, the prompt block, counters, I/O buffers: saved with their bytes; activations and
 workspaces: size only).  `vsd_plan_load` allocates the regions, uploads the saved bytes, patches the pointers, replays the calls
 under stream capture and keeps the graph; `vsd_plan_infer` is upload, launch, download.  Same kernels, same arguments: the frame a plan
-produces is bit for bit the engine's (tests/test_plan_gpu.py).  A plan is one (size, steps, strength, ControlNet scale, prompt, frames
-per launch); the reference's per-frame options (videopipeline.py:75-128) mean another plan.
+produces is bit for bit the engine's (tests/test_plan_gpu.py).
 
-File (little endian): "VSDPLAN1", u32 version, H, W, batch, n_regions, n_calls, u32 in_region, u64 in_offset, u32 out_region, u64
-out_offset, u32 prompt_region, u64 prompt_offset, u64 prompt_bytes (the engine's prompt block: vsd_plan_load_prompt replaces its bytes
-with another prompt's, `export_prompt`); regions: u64 size, u32 saved, u32 0; calls: u32 entry point (PLAN_FUNCS index), u32 nargs, args of 16 bytes
+A plan is one (size, steps, frames per launch): prompt (`export_prompt` / vsd_plan_load_prompt), strength and ControlNet scale
+(vsd_plan_set_options) change on the loaded plan.
+
+LIVE OPTIONS.  Three things in a prepared program depend on strength / controlnet_scale, all written by Engine._write_constants: the
+fp32 constant block, and per network the per-step time-embedding table.  LCM timesteps take only the 50 values 19, 39, ... 999, so
+`export_plan` computes, with the engine's own code, a 50-row time table per network (Engine._time_embeddings in chunks of exactly n
+rows -- the launch shape, and so the tuned kernel form and split, of the engine's own call: a row is bit for bit what the engine writes
+for that timestep), a coefficient table fp32 [50][6] (sqrt(a_t), sqrt(1 - a_t), c_skip, c_out and the two add-noise values, from
+lcm.LCMSchedule.step_coef / add_noise_coef) followed by fp32 logspace(-1, 0, nres), and records where the live block and tables sit.
+vsd_plan_set_options picks rows: one small launch, stream-ordered.
+
+LANES.  Regions that hold network weight tensors and nothing else (found by walking the engine's NetWeights / TAESDWeights) are
+flagged read-only: vsd_plan_clone_lane shares them between the plans of a process instead of uploading them once per lane.
+
+File (little endian), format version 2 (FORMAT_VERSION; VERSION = 1 names the base layout both versions share: the fixed fields, the
+region records and the call encoding, which did not change): "VSDPLAN1", u32 version, H, W, batch, n_regions, n_calls, u32 in_region, u64 in_offset, u32
+out_region, u64 out_offset, u32 prompt_region, u64 prompt_offset, u64 prompt_bytes (the engine's prompt block: vsd_plan_load_prompt
+replaces its bytes with another prompt's, `export_prompt`) -- HEADER_BYTES = 76, as in version 1.  Version 2 puts its EXTENSION right
+behind these fixed fields, in front of the region table (the loader has everything it checks before it allocates, and a reader of the
+fixed fields finds them where version 1 had them): u32 bytes of the extension that follow, u32 interface version (lib.VERSION), u64
+signature hash (FNV-1a of `signature_tags()`), then the options section: u32 n (timesteps of the program), u32 steps, u32 nres, u32
+number of time tables, f64 strength, f64 controlnet_scale (as exported), u32 region of the live constant block, u32 region of the
+coefficient table, u64 offset of each, then per time table (unet, cn, ref as the program has them) u32 region of the 50-row table, u32
+region of the live table, u64 offset of each, u64 row stride of the live table, u64 row bytes (= the 50-row table's stride).
+Regions: u64 size, u32 saved, u32 flags (bit 0: read-only network weights, shareable between lanes; version 1: 0).  Calls: u32 entry
+point (PLAN_FUNCS index), u32 nargs, args of 16 bytes
 (u32 tag, u32 aux, u64 value): 0 int32, 1 float32 bits, 2 pointer (aux = region, value = offset), 3 null, 4 the plan's stream,
 5 descriptor array (aux = count, value = bytes; followed by the bytes, u32 nfix, nfix x (u32 byte offset, u32 region, u64 offset));
-then the bytes of the saved regions in order."""
+then the bytes of the saved regions in order.  `file_offsets` finds the parts of a file.  Version 1 files (no extension, no flags)
+still load; they have no live options and share nothing."""
 import bisect
 import ctypes as C
 import struct
@@ -26,12 +49,56 @@ import torch
 from . import lib as L
 
 MAGIC = b"VSDPLAN1"
-VERSION = 1
+VERSION = 1               # the base layout (magic, fixed fields, region records, calls): what every reader of either version parses
+FORMAT_VERSION = 2        # what `export_plan` writes: the base layout plus the extension and the region flags
+HEADER_BYTES = 76         # the fixed fields (both versions)
+EXT_FIXED_BYTES = 16      # version 2, behind them: u32 bytes that follow, u32 interface version, u64 signature hash ...
+OPT_FIXED_BYTES = 56      # ... and the options section: its fixed part,
+OPT_TABLE_BYTES = 40      # and one record per time table
+REGION_BYTES = 16         # a region record
+ARG_BYTES = 16            # an argument of a call (after the call's u32 entry point, u32 nargs)
+REGION_SHARED = 1         # region flag, bit 0: read-only network weights, shareable between lanes
+OPT_ROWS = 50             # timesteps an LCM schedule can hold: 19, 39, ... 999
+OTHER_PROGRAM = 1         # include/vsd.h VSD_PLAN_OTHER_PROGRAM
 # entry points a frame program may call, by id (csrc/plan_dispatch.inc is generated from this list: scripts/gen_plan_dispatch.py)
 PLAN_FUNCS = ["vsd_preprocess_rgb", "vsd_sobel_control", "vsd_conv_gemm", "vsd_conv_gemm_group", "vsd_pair_begin", "vsd_pair_join",
               "vsd_pair_end", "vsd_groupnorm", "vsd_groupnorm_batched", "vsd_attention", "vsd_attention_batched", "vsd_tail_a", "vsd_tail_b",
               "vsd_add_noise_dev", "vsd_lcm_step_dev", "vsd_postprocess_rgb", "vsd_adain", "vsd_layernorm"]
 T_I32, T_F32, T_PTR, T_NULL, T_STREAM, T_DESC = range(6)
+
+
+def signature_tags():
+    """per PLAN_FUNCS entry "name:tags", one letter per argument after the context: p pointer, i int32, f float, d descriptor array,
+    o optional int output (null in a plan) -- what vsd_plan_load checks a recorded call against (csrc/plan_dispatch.inc)"""
+    letter = {C.c_void_p: "p", C.c_int: "i", C.c_int32: "i", C.c_float: "f", C.POINTER(L.ConvDesc): "d", C.POINTER(C.c_int): "o"}
+    return [name + ":" + "".join(letter[t] for t in L.SIGNATURES[name][1][1:]) for name in PLAN_FUNCS]
+
+
+def signature_hash() -> int:
+    """64-bit FNV-1a of the lines of `signature_tags`, each followed by a newline: a file written against other signatures is refused"""
+    h = 0xCBF29CE484222325
+    for b in "".join(line + "\n" for line in signature_tags()).encode():
+        h = ((h ^ b) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def file_offsets(data: bytes) -> dict:
+    """byte offsets of the parts of a plan file's head: the extension and its fields (version 2), the region table, the call list"""
+    version, = struct.unpack_from("<I", data, 8)
+    nreg, = struct.unpack_from("<I", data, 24)
+    o = {"version": 8, "ext": None, "interface_version": None, "signature_hash": None, "options": None, "options_end": None}
+    regions = HEADER_BYTES
+    if version >= 2:
+        ext, = struct.unpack_from("<I", data, HEADER_BYTES)
+        o.update(ext=HEADER_BYTES, interface_version=HEADER_BYTES + 4, signature_hash=HEADER_BYTES + 8, options=HEADER_BYTES + EXT_FIXED_BYTES)
+        regions = HEADER_BYTES + 4 + ext
+        o["options_end"] = regions
+    o["regions"] = regions
+    o["calls"] = regions + nreg * REGION_BYTES
+    o["first_arg"] = o["calls"] + 8  # (u32 tag, u32 aux, u64 value) of the first call's first argument
+    return o
+
+
 _PTR_FIELDS = [(name, getattr(L.ConvDesc, name).offset) for name, t in L.ConvDesc._fields_ if t is C.c_void_p]
 
 
@@ -53,9 +120,14 @@ class _Regions:
         self.blocks = blocks
         self.used = {}  # block index -> region id
 
-    def locate(self, ptr: int):
+    def find(self, ptr: int):
+        """index of the allocation that holds `ptr` (None: no live one)"""
         i = bisect.bisect_right(self.starts, ptr) - 1
-        if i < 0 or ptr >= self.blocks[i][0] + self.blocks[i][1]:
+        return None if i < 0 or ptr >= self.blocks[i][0] + self.blocks[i][1] else i
+
+    def locate(self, ptr: int):
+        i = self.find(ptr)
+        if i is None:
             raise RuntimeError(f"plan export: device pointer {ptr:#x} lies in no live allocation of this process")
         rid = self.used.setdefault(i, len(self.used))
         return rid, ptr - self.blocks[i][0]
@@ -77,6 +149,71 @@ class _LibProxy:
             return fn(h, joined)
 
         return pair_end
+
+
+def _weight_tensors(obj, seen):
+    """every tensor reachable from a NetWeights / TAESDWeights object (its packed layers, norms, raw cross-attention weights) -- not
+    through `ops`, which holds workspaces"""
+    if obj is None or id(obj) in seen:
+        return
+    seen.add(id(obj))
+    if isinstance(obj, torch.Tensor):
+        yield obj
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            yield from _weight_tensors(v, seen)
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            yield from _weight_tensors(v, seen)
+    elif type(obj).__module__.startswith(__package__ + ".") and hasattr(obj, "__dict__"):
+        for k, v in vars(obj).items():
+            if k != "ops":
+                yield from _weight_tensors(v, seen)
+
+
+def option_coefficients(nres: int) -> torch.Tensor:
+    """fp32 [50][6] per timestep 19, 39, ... 999 -- sqrt(a_t), sqrt(1 - a_t), c_skip, c_out, the two add-noise values, by
+    lcm.LCMSchedule.step_coef / add_noise_coef themselves -- followed by logspace(-1, 0, nres): what vsd_plan_set_options builds the
+    constant block of any schedule from (step i takes columns 0..3 of its timestep's row and columns 0..1 of the next step's)"""
+    from .lcm import LCMSchedule, lcm_timesteps
+
+    sched = LCMSchedule(1.0, 1)
+    rows = []
+    for t in sorted(lcm_timesteps(1.0, OPT_ROWS)):
+        sched.timesteps = [t]
+        rows.append(list(sched.step_coef(0)[:4]) + list(sched.add_noise_coef()))
+    return torch.cat([torch.tensor(rows, dtype=torch.float32).reshape(-1), torch.logspace(-1, 0, nres)])
+
+
+def _option_tables(engine):
+    """The option-dependent constants of EVERY schedule the program can run (module docstring, LIVE OPTIONS), by the code that computes
+    them for one schedule today: [(name, live table, 50-row table)], the coefficient table with the logspace behind it, nres."""
+    from .lcm import LCMSchedule, lcm_timesteps
+
+    ops, p = engine.ops, engine.plan
+    n = p["n"]
+    every = sorted(lcm_timesteps(1.0, OPT_ROWS))  # 19, 39, ... 999: row j holds timestep 20 j + 19
+    assert len(every) == OPT_ROWS and all(t == 20 * j + 19 for j, t in enumerate(every))
+    sched = LCMSchedule(1.0, 1)
+    nets = [("unet", engine.unet, True)] + ([("cn", engine.cn, True)] if p["cn"] and engine.cn is not None else [])
+    if engine.shared.get("ref_mode"):
+        nets.append(("ref", engine.unet, False))
+    tables = []
+    for name, net, use_cond in nets:
+        live = engine.shared["temb"][name]
+        table = ops.zeros(OPT_ROWS, live.shape[1], dtype=live.dtype)
+        chunk = ops.zeros(*live.shape, dtype=live.dtype)  # an allocation like the live table: the engine's own launch
+        for r0 in range(0, OPT_ROWS, n):
+            ts = every[r0:r0 + n]
+            sched.timesteps = ts + [ts[-1]] * (n - len(ts))
+            engine._time_embeddings(net, sched, chunk, use_cond=use_cond)
+            with torch.cuda.stream(ops.stream):
+                table[r0:r0 + len(ts)].copy_(chunk[:len(ts)])
+        tables.append((name, live, table))
+    nres = 13 if engine.cn is None else len(engine.cn.zero_convs) + 1
+    coef_dev = ops.to_device(option_coefficients(nres))
+    ops.synchronize()
+    return tables, coef_dev, nres
 
 
 def export_plan(engine, path: str) -> dict:
@@ -111,6 +248,7 @@ def export_plan(engine, path: str) -> dict:
         ops.synchronize()
     finally:
         ctx.call, ctx.lib = orig_call, orig_lib
+    tables, coef_dev, nres = _option_tables(engine)
     regs = _Regions(ops.device.index if hasattr(ops.device, "index") and ops.device.index is not None else 0)
     stream = ops.s.value
     if not stream:
@@ -162,19 +300,41 @@ def export_plan(engine, path: str) -> dict:
     # what is scratch (no bytes saved): the activation arena and the op workspaces
     scratch = {t.data_ptr() for t in engine.arena.chunks}
     scratch |= {t.data_ptr() for t in ops._ws.values()}
-    order = sorted(regs.used.items(), key=lambda kv: kv[1])
     p = engine.plan
+    # the options section: where the live constants sit and where the tables to pick their rows from
+    consts = engine.shared["consts"]
+    c_r, c_off = regs.locate(consts.data_ptr())
+    k_r, k_off = regs.locate(coef_dev.data_ptr())
+    opts = struct.pack("<IIIIdd", p["n"], p["steps"], nres, len(tables), float(p["strength"]), float(p["cn_scale"]))
+    opts += struct.pack("<IIQQ", c_r, k_r, c_off, k_off)
+    for name, live, table in tables:
+        t_r, t_off = regs.locate(table.data_ptr())
+        l_r, l_off = regs.locate(live.data_ptr())
+        assert live.stride(1) == 1 and table.is_contiguous()
+        opts += struct.pack("<IIQQQQ", t_r, l_r, t_off, l_off, live.stride(0) * live.element_size(), table.shape[1] * table.element_size())
+    assert len(opts) == OPT_FIXED_BYTES + OPT_TABLE_BYTES * len(tables)
+    ext = struct.pack("<IQ", L.VERSION, signature_hash()) + opts
+    # what may be shared between lanes: allocations that hold a network's weight tensor -- and are nothing the program writes
+    private = [engine.pblock.buf, consts, coef_dev, engine.noise, engine.frame_u8, engine.out_u8, engine.edge_u8, getattr(engine, "noise_ref", None),
+               getattr(engine, "ref_u8", None)] + [t for _, live, table in tables for t in (live, table)] + list(engine.shared["temb"].values())
+    never = {regs.find(t.untyped_storage().data_ptr()) for t in private if t is not None} | {regs.find(s) for s in scratch}
+    seen = set()
+    weights = {regs.find(t.untyped_storage().data_ptr()) for net in (engine.unet, engine.cn, engine.vae) for t in _weight_tensors(net, seen) if t.is_cuda}
+    shared = (weights - never) & set(regs.used)
+    order = sorted(regs.used.items(), key=lambda kv: kv[1])
     with open(path, "wb") as f:
         f.write(MAGIC)
-        f.write(struct.pack("<IIIIII", VERSION, p["H"], p["W"], p["batch"], len(order), len(calls)))
+        f.write(struct.pack("<IIIIII", FORMAT_VERSION, p["H"], p["W"], p["batch"], len(order), len(calls)))
         f.write(struct.pack("<IQIQ", in_r, in_off, out_r, out_off))
         f.write(struct.pack("<IQQ", pr_r, pr_off, engine.pblock.buf.numel()))
+        assert f.tell() == HEADER_BYTES
+        f.write(struct.pack("<I", len(ext)) + ext)
         saved = []
         for bi, rid in order:
             addr, size = regs.blocks[bi]
             keep = not any(addr <= s < addr + size for s in scratch)
             saved.append(keep)
-            f.write(struct.pack("<QII", size, int(keep), 0))
+            f.write(struct.pack("<QII", size, int(keep), REGION_SHARED if keep and bi in shared else 0))
         f.write(body)
         hip = C.CDLL("libamdhip64.so")
         hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -188,7 +348,8 @@ def export_plan(engine, path: str) -> dict:
                 raise RuntimeError(f"plan export: hipMemcpy of a {size}-byte region failed ({rc})")
             f.write(host.tobytes())
     return {"regions": len(order), "saved_bytes": sum(regs.blocks[bi][1] for (bi, _), k in zip(order, saved) if k),
-            "scratch_bytes": sum(regs.blocks[bi][1] for (bi, _), k in zip(order, saved) if not k), "calls": len(calls)}
+            "scratch_bytes": sum(regs.blocks[bi][1] for (bi, _), k in zip(order, saved) if not k), "calls": len(calls),
+            "shared_bytes": sum(regs.blocks[bi][1] for (bi, _), k in zip(order, saved) if k and bi in shared), "options": True}
 
 
 PROMPT_MAGIC = b"VSDPRMT1"
@@ -207,10 +368,14 @@ def export_prompt(pblock, path: str) -> int:
 class CPlan:
     """vsd_plan_load / vsd_plan_infer through ctypes (tests, examples): what a C host does with a plan file"""
 
-    def __init__(self, path: str, device_id: int = 0):
-        self.ctx = L.Context(device_id)
+    def __init__(self, path: str, device_id: int = 0, lane: int = -1, _clone_of=None):
         h = C.c_void_p()
-        self.ctx.call("vsd_plan_load", path.encode(), C.byref(h))
+        if _clone_of is None:
+            self.ctx = L.Context(device_id)
+            self.ctx.call("vsd_plan_load_lane", path.encode(), lane, C.byref(h))
+        else:  # (a clone lives in its source's context)
+            self.ctx = _clone_of.ctx
+            self.ctx.call("vsd_plan_clone_lane", _clone_of.h, lane, C.byref(h))
         self.h = h
         dims = (C.c_int * 3)()
         self.ctx.call("vsd_plan_info", self.h, dims)
@@ -257,6 +422,26 @@ class CPlan:
 
     def load_prompt(self, path: str):
         self.ctx.call("vsd_plan_load_prompt", self.h, path.encode())
+
+    def set_options(self, strength: float, controlnet_scale: float) -> bool:
+        """vsd_plan_set_options: Engine.update_options for a loaded plan -- stream-ordered, no re-capture.  False (and nothing changed)
+        when the strength needs another program: another number of timesteps than the plan's."""
+        rc = self.ctx.lib.vsd_plan_set_options(self.ctx.h, self.h, float(strength), float(controlnet_scale))
+        if rc == OTHER_PROGRAM:
+            return False
+        self.ctx.check(rc, "vsd_plan_set_options")
+        return True
+
+    def clone(self, lane: int = -1) -> "CPlan":
+        """vsd_plan_clone_lane: a further plan of this program on launch stream `lane` that shares this one's weights; it starts with
+        this plan's current prompt and options and keeps its own afterwards"""
+        return CPlan(None, lane=lane, _clone_of=self)
+
+    def memory(self):
+        """vsd_plan_memory: (bytes of the regions this plan owns, bytes of the regions it shares with its clones)"""
+        out = (C.c_uint64 * 2)()
+        self.ctx.call("vsd_plan_memory", self.h, out)
+        return int(out[0]), int(out[1])
 
     def close(self):
         if getattr(self, "h", None):
