@@ -3,12 +3,14 @@
  * size / step count / prompt / frames per launch).
  *
  *   gcc -O2 examples/plan_host.c -Iinclude -Lvideosd_amd -lvsd -Wl,-rpath,$PWD/videosd_amd -o /tmp/plan_host
- *   /tmp/plan_host frame.vsdplan in.raw out.raw [launches] [lanes] [strength controlnet_scale]
+ *   /tmp/plan_host [--seed N] frame.vsdplan in.raw out.raw [launches] [lanes] [strength controlnet_scale]
  * in.raw / out.raw: uint8 [frames per launch][H][W][3].  lanes (1..4): that many plans of the program in flight, one per launch
  * stream (the reference keeps N actors per node, server.py:132-137; inside one process the launch lanes do the same) -- frame k goes
  * to lane k mod lanes.  The file is read ONCE: lane 0 loads it, the other lanes are clones that share its weights on the device
  * (vsd_plan_clone_lane).  strength controlnet_scale: the reference's live options (server.py:163-197), applied to every lane with
- * vsd_plan_set_options before the timed loop.  Prints the frame rate; out.raw is lane 0's last result.
+ * vsd_plan_set_options before the timed loop.  --seed N (anywhere on the line; a plan exported with device_seed only): every frame of
+ * every launch is denoised with the noise of seed N (vsd_plan_set_seeds; the client's seed box, server.py:181-182).  Prints the frame
+ * rate; out.raw is lane 0's last result.
  * (the reference's caller is a Python loop, server.py:104-143; this is that loop for a C / C++ / Go-via-cgo media server) */
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,8 +20,18 @@
 #include "vsd.h"
 
 int main(int argc, char** argv) {
+  int have_seed = 0;
+  uint64_t seed = 0;
+  for (int i = 1; i + 1 < argc; ++i)
+    if (strcmp(argv[i], "--seed") == 0) {  /* taken out of the line: the positional arguments keep their places */
+      have_seed = 1;
+      seed = strtoull(argv[i + 1], NULL, 0);
+      memmove(argv + i, argv + i + 2, (size_t)(argc - i - 2) * sizeof(char*));
+      argc -= 2;
+      break;
+    }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s plan in.raw out.raw [launches] [lanes] [strength controlnet_scale]\n", argv[0]);
+    fprintf(stderr, "usage: %s [--seed N] plan in.raw out.raw [launches] [lanes] [strength controlnet_scale]\n", argv[0]);
     return 2;
   }
   const int launches = argc > 4 ? atoi(argv[4]) : 1;
@@ -44,6 +56,11 @@ int main(int argc, char** argv) {
       if (orc != VSD_OK) { fprintf(stderr, "%s\n", vsd_last_error(ctx)); return 1; }
     }
     vsd_plan_info(ctx, plan[l], dims);
+    if (have_seed) {  /* one seed per frame of the launch; stream-ordered like the options */
+      uint64_t seeds[1024];
+      for (int b = 0; b < dims[2] && b < 1024; ++b) seeds[b] = seed;
+      if (vsd_plan_set_seeds(ctx, plan[l], seeds, dims[2]) != VSD_OK) { fprintf(stderr, "%s\n", vsd_last_error(ctx)); return 1; }
+    }
     n = (size_t)dims[2] * dims[0] * dims[1] * 3;
     in[l] = vsd_pinned_alloc(ctx, n);
     out[l] = vsd_pinned_alloc(ctx, n);

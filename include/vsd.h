@@ -52,10 +52,10 @@ enum vsd_family {
   VSD_FAM_ATTENTION = 4, VSD_FAM_ELEMENTWISE = 5, VSD_FAM_COUNT = 6
 };
 
-/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2) and the size in
+/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
-#define VSD_VERSION 9
+#define VSD_VERSION 10
 int vsd_version(void);
 int vsd_conv_desc_size(void);
 
@@ -250,6 +250,34 @@ int vsd_add_noise_dev(vsd_ctx* ctx, const void* x0, const void* noise_f32, const
 int vsd_lcm_step_dev(vsd_ctx* ctx, const void* eps, const void* sample, const void* noise_f32, const void* coef_dev, int hw,
                      int batch, void* prev, void* denoised, void* dec_in, void* stream);
 
+/* ---- seeded noise on the device (csrc/noise.hip) ------------------------------------------------------------------------------------
+ * The reference's frame loop sends `seed` with every frame (server.py:181-182) and on its CUDA deployment the seed reaches the initial
+ * noise.  The default here keeps the CPU-contract draws of Engine.host_noise (one table per plan, the same for every frame); with these
+ * entry points the noise is instead a pure function of (seed, kind, draw, pixel, channel), evaluated inside the captured program.
+ * THE NOISE CONTRACT (fixed; kernels and tests are held to it, the integers bit for bit):
+ *   - `seed` is taken modulo 2^64; the Philox key is (low 32 bits, high 32 bits).
+ *   - kind 0: the frame's noise; kind 1: the draws of the reference-only mode's reference latents.
+ *   - kind 0: draw d = 0 is the prepare_latents noise, d = k the draw scheduler step k - 1 adds (noise[i + 1] of Engine.host_noise);
+ *     kind 1: d = the step index.
+ *   - latent pixel i (row-major, y * w0 + x): X[0..3] = Philox4x32-10 with counter (i, d, kind, 0) and the key above (multipliers
+ *     0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, 10 rounds: the Random123 generator, its known answers hold).
+ *   - u(x) = ((x >> 9) + 0.5) * 2^-23: exact in fp32, never 0 or 1.
+ *   - Box-Muller in fp32 with the precise logf / sincosf: r = sqrtf(-2 logf(u(X0))), t = fp32(2 pi) * u(X1); channels 0 and 1 are
+ *     r cos t and r sin t; channels 2 and 3 the same from (X2, X3).  |z| <= sqrt(48 ln 2) = 5.77.
+ *   - nothing else enters: not the frames per launch, the place in the launch, the lane, the frames before, Python or a plan file.
+ *   This is NOT torch's CUDA stream for the same seed (that mapping depends on the device's grid size).
+ * vsd_noise_fill: one draw of hw pixels; raw = 0: fp32 [4][hw], the layout vsd_add_noise_dev / vsd_lcm_step_dev read (out 4-byte
+ *   aligned); raw = 1: the integers X as u32 [hw][4] (out 16-byte aligned).
+ * vsd_add_noise_seeded / vsd_lcm_step_seeded: vsd_add_noise_dev / vsd_lcm_step_dev -- the same arithmetic, operation for operation, the
+ *   same bits as vsd_noise_fill followed by them -- with the noise pointer replaced by (seeds_dev: u32 [batch][2] = (low, high) per
+ *   image in DEVICE memory, kind, draw): image b of the launch uses seeds_dev[b].  vsd_lcm_step_seeded: draw <= 0 = this step adds no
+ *   noise (vsd_lcm_step_dev with noise_f32 NULL; seeds_dev may then be NULL). */
+int vsd_noise_fill(vsd_ctx* ctx, uint32_t seed_lo, uint32_t seed_hi, int kind, int draw, int hw, int raw, void* out, void* stream);
+int vsd_add_noise_seeded(vsd_ctx* ctx, const void* x0, const void* seeds_dev, int kind, int draw, const void* coef_dev, int hw, int batch,
+                         void* out, void* stream);
+int vsd_lcm_step_seeded(vsd_ctx* ctx, const void* eps, const void* sample, const void* seeds_dev, int kind, int draw, const void* coef_dev,
+                        int hw, int batch, void* prev, void* denoised, void* dec_in, void* stream);
+
 /* AdaIN of the reference-only mode (lcm_reference_pipeline.py:593-603, dead at v2 but still exposed as `ref`):
  * out[r][c] = (x[r][c] - mean_c) / std_c * std_ref_c + mean_ref_c, statistics over the `rows` pixels of one image,
  * population variance clamped at eps before the square root.  stats / stats_ref: fp32 [c][2] per-channel (sum, sum of
@@ -410,6 +438,13 @@ int vsd_plan_load_prompt(vsd_ctx* ctx, vsd_plan* plan, const char* path);
  * entries; VSD_ERR_ARG for steps < 1 or an empty schedule. */
 int vsd_lcm_timesteps(double strength, int steps, int* out, int* n);
 int vsd_plan_set_options(vsd_ctx* ctx, vsd_plan* plan, double strength, double controlnet_scale);
+/* PER-FRAME SEEDS.  A plan exported from an engine prepared with device_seed (its program calls vsd_add_noise_seeded /
+ * vsd_lcm_step_seeded) reads one seed per frame of the launch from a small device buffer of its own (every clone has its own).
+ * vsd_plan_set_seeds: seeds[0 .. n) on the HOST, n = the plan's frames per launch, written on the plan's stream by one small launch per 32 seeds (the values
+ * travel as kernel arguments: the array may be reused when the call returns, and nothing waits): stream-ordered like
+ * vsd_plan_set_options -- frames submitted before the call keep their seeds.  A fresh plan holds the seeds of the engine at export.  VSD_ERR_ARG with a reason for
+ * another n and for a plan whose program holds no seeded noise.  The frames are bit for bit the Python engine's for the same seeds. */
+int vsd_plan_set_seeds(vsd_ctx* ctx, vsd_plan* plan, const uint64_t* seeds, int n);
 /* LANES THAT SHARE WEIGHTS.  A second plan of the same program on launch stream `lane` (0..3, or -1 for a stream of its own) without
  * reading the file again: the regions the exporter flagged as read-only network weights are SHARED with the source (reference-counted:
  * freed with the last plan, whatever the order of vsd_plan_free); counters, constants, time tables, prompt block, frame buffers and

@@ -1,0 +1,165 @@
+// Seeded noise on the device (include/vsd.h, THE NOISE CONTRACT): the normal draws of a frame as a pure function of
+// (seed, kind, draw, pixel, channel) -- Philox4x32-10, one block per latent pixel = its four channels, Box-Muller in fp32 -- evaluated
+// in the thread that uses them.  vsd_noise_fill writes a draw out (the layout vsd_add_noise_dev / vsd_lcm_step_dev read, or the raw
+// integers); vsd_add_noise_seeded / vsd_lcm_step_seeded are those two kernels with the noise pointer replaced by per-image seeds in
+// device memory: a captured graph then follows a new seed per frame with an 8-byte copy per image, nothing re-captured.
+// Launch-bound like the rest of the scheduler arithmetic (at most batch * hw = 5 * 4096 threads at 512 x 512): 10 fixed rounds of two
+// 32 x 32 -> 64 multiplies (a v_mul_lo_u32 / v_mul_hi_u32 pair each, quarter rate), no data-dependent trip count, one thread per pixel.
+#include <stdarg.h>
+
+#include "common.h"
+
+// The seeded scheduler kernels must give the bits of add_noise_dev_kernel / lcm_step_dev_kernel (csrc/elementwise.hip), whose source
+// leaves the choice of what becomes an fma to the compiler (fp-contract "fast" is hipcc's default), and that choice follows the code
+// around an expression: a kernel with the same source text but no noise branch got mul, mul, add where the _dev kernel has mul, fma.
+// So nothing in this file is contracted, and the fused operations of the _dev kernels' gfx950 code are written out where they occur.
+#pragma clang fp contract(off)
+
+namespace {
+
+struct Philox4 {
+  uint32_t x[4];
+};
+
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+// ((x >> 9) + 0.5) * 2^-23: every step exact in fp32, never 0 or 1
+__device__ __forceinline__ float philox_u01(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
+
+struct Normal4 {
+  float z[4];
+};
+
+// the four channels of pixel i of draw (seed, kind, d): what all three entry points share
+__device__ __forceinline__ Normal4 seeded_normals(uint32_t seed_lo, uint32_t seed_hi, uint32_t kind, uint32_t d, uint32_t i, Philox4* raw = nullptr) {
+  const Philox4 p = philox4x32_10(i, d, kind, 0u, seed_lo, seed_hi);
+  if (raw) *raw = p;
+  Normal4 n;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float r = sqrtf(-2.0f * logf(philox_u01(p.x[2 * h])));
+    float s, c;
+    sincosf(6.283185307179586f * philox_u01(p.x[2 * h + 1]), &s, &c);
+    n.z[2 * h] = __fmul_rn(r, c);
+    n.z[2 * h + 1] = __fmul_rn(r, s);
+  }
+  return n;
+}
+
+__global__ void noise_fill_kernel(uint32_t seed_lo, uint32_t seed_hi, uint32_t kind, uint32_t draw, int hw, int raw, void* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= hw) return;
+  Philox4 p;
+  const Normal4 n = seeded_normals(seed_lo, seed_hi, kind, draw, (uint32_t)i, &p);
+  if (raw) {
+    reinterpret_cast<uint4*>(out)[i] = make_uint4(p.x[0], p.x[1], p.x[2], p.x[3]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) reinterpret_cast<float*>(out)[(size_t)c * hw + i] = n.z[c];
+  }
+}
+
+struct StepCoef {
+  float sa, sb, cskip, cout, sap, sbp;
+};
+
+// add_noise_dev_kernel (csrc/elementwise.hip), operation for operation as compiled (sa * x + sb * n is fma(sa, x, sb * n) there), with
+// the draw computed here; blockIdx.y = image of the launch
+__global__ void add_noise_seeded_kernel(const half_t* __restrict__ x0, const uint32_t* __restrict__ seeds, uint32_t kind, uint32_t draw,
+                                        const float* __restrict__ coef, int hw, half_t* __restrict__ out) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= hw) return;
+  const float sa = coef[0], sb = coef[1];
+  const Normal4 nz = seeded_normals(seeds[2 * blockIdx.y], seeds[2 * blockIdx.y + 1], kind, draw, (uint32_t)i);
+  const size_t row = (size_t)blockIdx.y * hw + i;
+  half8 x = *reinterpret_cast<const half8*>(x0 + row * 8);
+  half8 o = (half8){0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int c = 0; c < 4; ++c) o[c] = (half_t)__builtin_fmaf(sa, (float)x[c], sb * nz.z[c]);
+  *reinterpret_cast<half8*>(out + row * 8) = o;
+}
+
+// lcm_step_dev_kernel (csrc/elementwise.hip), operation for operation as compiled: xs - sb * e and cout * px0 + cskip * xs are one fma
+// each, sap * d + sbp * n is not.  NOISE = false: the step that adds none (its noise pointer NULL)
+template <bool NOISE>
+__global__ void lcm_step_seeded_kernel(const half_t* __restrict__ eps, const half_t* __restrict__ sample, const uint32_t* __restrict__ seeds,
+                                       uint32_t kind, uint32_t draw, const float* __restrict__ coef, int hw, half_t* __restrict__ prev,
+                                       half_t* __restrict__ den, half_t* __restrict__ dec_in) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= hw) return;
+  const StepCoef k = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+  Normal4 nz = {{0.f, 0.f, 0.f, 0.f}};
+  if (NOISE) nz = seeded_normals(seeds[2 * blockIdx.y], seeds[2 * blockIdx.y + 1], kind, draw, (uint32_t)i);
+  const size_t row = (size_t)blockIdx.y * hw + i;
+  half8 e = *reinterpret_cast<const half8*>(eps + row * 8);
+  half8 x = *reinterpret_cast<const half8*>(sample + row * 8);
+  half8 op = (half8){0, 0, 0, 0, 0, 0, 0, 0}, od = op, oi = op;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float xs = (float)x[c];
+    float px0 = __builtin_fmaf(-k.sb, (float)e[c], xs) / k.sa;
+    float d = __builtin_fmaf(k.cskip, xs, k.cout * px0);
+    asm volatile("" : "+v"(d));  // d exists in fp32 before it is rounded to fp16, as there: no v_fma_mixlo_f16 (emits nothing)
+    od[c] = (half_t)d;
+    float pv = NOISE ? k.sap * d + k.sbp * nz.z[c] : d;  // (mul, mul, add there too)
+    op[c] = (half_t)pv;
+    oi[c] = (half_t)(tanhf((float)od[c] / 3.0f) * 3.0f);
+  }
+  if (prev) *reinterpret_cast<half8*>(prev + row * 8) = op;
+  if (den) *reinterpret_cast<half8*>(den + row * 8) = od;
+  if (dec_in) *reinterpret_cast<half8*>(dec_in + row * 8) = oi;
+}
+
+}  // namespace
+
+extern "C" int vsd_noise_fill(vsd_ctx* ctx, uint32_t seed_lo, uint32_t seed_hi, int kind, int draw, int hw, int raw, void* out, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!out || hw <= 0 || kind < 0 || draw < 0 || (raw != 0 && raw != 1) || ((uintptr_t)out & (raw ? 15 : 3)))
+    return vsd_fail(ctx, VSD_ERR_ARG, "noise_fill: bad arguments (hw >= 1, kind >= 0, draw >= 0, raw 0 or 1, out aligned to %d bytes)", raw ? 16 : 4);
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  hipLaunchKernelGGL(noise_fill_kernel, dim3(cdiv(hw, 256)), dim3(256), 0, s, seed_lo, seed_hi, (uint32_t)kind, (uint32_t)draw, hw, raw, out);
+  return ls.finish();
+}
+
+extern "C" int vsd_add_noise_seeded(vsd_ctx* ctx, const void* x0, const void* seeds_dev, int kind, int draw, const void* coef_dev, int hw, int batch,
+                                    void* out, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!x0 || !seeds_dev || !coef_dev || !out || hw <= 0 || batch < 1 || batch > 65535 || kind < 0 || draw < 0)
+    return vsd_fail(ctx, VSD_ERR_ARG, "add_noise_seeded: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  hipLaunchKernelGGL(add_noise_seeded_kernel, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)x0, (const uint32_t*)seeds_dev,
+                     (uint32_t)kind, (uint32_t)draw, (const float*)coef_dev, hw, (half_t*)out);
+  return ls.finish();
+}
+
+extern "C" int vsd_lcm_step_seeded(vsd_ctx* ctx, const void* eps, const void* sample, const void* seeds_dev, int kind, int draw, const void* coef_dev,
+                                   int hw, int batch, void* prev, void* denoised, void* dec_in, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!eps || !sample || !coef_dev || hw <= 0 || batch < 1 || batch > 65535 || kind < 0 || (draw > 0 && !seeds_dev))
+    return vsd_fail(ctx, VSD_ERR_ARG, "lcm_step_seeded: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  if (draw > 0)
+    hipLaunchKernelGGL(lcm_step_seeded_kernel<true>, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)eps, (const half_t*)sample,
+                       (const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw, (const float*)coef_dev, hw, (half_t*)prev, (half_t*)denoised,
+                       (half_t*)dec_in);
+  else
+    hipLaunchKernelGGL(lcm_step_seeded_kernel<false>, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)eps, (const half_t*)sample,
+                       (const uint32_t*)seeds_dev, 0u, 0u, (const float*)coef_dev, hw, (half_t*)prev, (half_t*)denoised, (half_t*)dec_in);
+  return ls.finish();
+}

@@ -44,6 +44,11 @@ constexpr int PLAN_NFUNCS = (int)(sizeof(PLAN_SIGS) / sizeof(PLAN_SIGS[0]));
 
 const char* plan_tags(int fn) { return strchr(PLAN_SIGS[fn], ':') + 1; }
 
+bool plan_fn_is(int fn, const char* name) {
+  const size_t n = strlen(name);
+  return strncmp(PLAN_SIGS[fn], name, n) == 0 && PLAN_SIGS[fn][n] == ':';
+}
+
 uint64_t plan_signature_hash() {  // FNV-1a over the lines, each followed by a newline (videosd_amd/plan.py signature_hash)
   uint64_t h = 0xCBF29CE484222325ull;
   for (int i = 0; i < PLAN_NFUNCS; ++i)
@@ -90,6 +95,10 @@ struct PlanProgram {
   uint32_t consts_r = 0, coef_r = 0;
   uint64_t consts_off = 0, coef_off = 0;
   std::vector<RawOptTable> tabs;
+  // per-frame seeds: where the program's vsd_add_noise_seeded calls read them (no field of the file: found in the call list)
+  bool seeded = false;
+  uint32_t seed_r = 0;
+  uint64_t seed_off = 0;
 };
 
 }  // namespace
@@ -122,6 +131,15 @@ int plan_dispatch(vsd_ctx* ctx, int fn, int n, const PlanArg* a) {
 #include "plan_dispatch.inc"
     default: return -1;
   }
+}
+
+// vsd_plan_set_seeds: up to 32 seeds per launch, by value
+struct SeedChunk {
+  uint64_t v[32];
+};
+__global__ void plan_set_seeds_kernel(uint64_t* __restrict__ dst, SeedChunk c, int n) {
+  const int i = threadIdx.x;
+  if (i < n) dst[i] = c.v[i];
 }
 
 struct Reader {
@@ -284,6 +302,17 @@ const char* plan_parse(FILE* f, PlanProgram& g) {
     if (desc_at >= 0) {
       const bool counted = desc_at + 1 < rc.n && tags[desc_at + 1] == 'i';
       if (counted ? (int)(int64_t)rc.a[desc_at + 1].val != desc_count : desc_count != 1) return "a descriptor array of another length than its call says";
+    }
+    // the seed buffer of a program with seeded noise: `seeds_dev` (argument 1) of its vsd_add_noise_seeded calls -- ONE buffer of 8 bytes
+    // per frame of the launch, in a saved region of the plan's own
+    if (plan_fn_is(rc.fn, "vsd_add_noise_seeded")) {
+      const RawArg& a = rc.a[1];
+      if (a.tag != T_PTR || a.val % 8 || !plan_inside(g, a.aux, a.val, 8ull * g.batch) || !g.saved[a.aux] || (g.flags[a.aux] & REGION_SHARED))
+        return "the seeds of a seeded noise call outside a region of the plan's own";
+      if (g.seeded && (g.seed_r != a.aux || g.seed_off != a.val)) return "seeded noise calls with different seed buffers";
+      g.seeded = true;
+      g.seed_r = a.aux;
+      g.seed_off = a.val;
     }
   }
   if (!plan_inside(g, g.in_r, g.in_off, (uint64_t)g.batch * g.H * g.W * 3) || !plan_inside(g, g.out_r, g.out_off, (uint64_t)g.batch * g.H * g.W * 3) ||
@@ -550,6 +579,29 @@ extern "C" int vsd_plan_set_options(vsd_ctx* ctx, vsd_plan* plan, double strengt
     a.tab[t] = {(const uint32_t*)at(r.table_r, r.table_off), (uint32_t*)at(r.live_r, r.live_off), (uint32_t)(r.row_bytes / 4), (uint32_t)(r.live_stride / 4)};
   }
   return plan_options_launch(ctx, plan->stream, a);
+}
+
+// one seed per frame of the launch for the frames submitted from now on: include/vsd.h
+extern "C" int vsd_plan_set_seeds(vsd_ctx* ctx, vsd_plan* plan, const uint64_t* seeds, int n) {
+  if (!ctx || !plan) return VSD_ERR_ARG;
+  const PlanProgram& g = *plan->prog;
+  if (!g.seeded)
+    return vsd_fail(ctx, VSD_ERR_ARG, "plan_set_seeds: the plan's program holds no seeded noise (export it from an engine prepared with device_seed)");
+  if (!seeds || n != plan->batch) return vsd_fail(ctx, VSD_ERR_ARG, "plan_set_seeds: %d seed(s) given, the plan takes %d frame(s) per launch", seeds ? n : 0, plan->batch);
+  // The values travel as kernel ARGUMENTS, 32 per launch: read when the call is made (the caller's array is free at once, pinned or
+  // not), written in stream order, and no copy from pageable memory that would wait for the frames in flight on this stream.
+  // (a u64 in memory is the (low, high) u32 pair the noise kernels read: little-endian, as the plan file itself)
+  uint64_t* dst = (uint64_t*)((char*)plan->regions[g.seed_r].get() + g.seed_off);
+  for (int at = 0; at < n; at += 32) {
+    SeedChunk c{};
+    const int m = std::min(32, n - at);
+    for (int i = 0; i < m; ++i) c.v[i] = seeds[at + i];
+    LaunchScope ls(ctx, plan->stream, VSD_FAM_ELEMENTWISE, 0.0);
+    hipLaunchKernelGGL(plan_set_seeds_kernel, dim3(1), dim3(64), 0, plan->stream, dst + at, c, m);
+    const int rc = ls.finish();
+    if (rc != VSD_OK) return rc;
+  }
+  return VSD_OK;
 }
 
 extern "C" int vsd_plan_info(vsd_ctx* ctx, vsd_plan* plan, int* dims) {

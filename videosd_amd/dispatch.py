@@ -325,6 +325,15 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
     if shm is not None:
         rings = (_ShmRing(shm["slots"], shm["slot_bytes"], shm["in"]), _ShmRing(shm["slots"], shm["slot_bytes"], shm["out"]))
     pipelined = max_batch > 1 and hasattr(pipe, "submit_batch") and hasattr(pipe, "collect_batch")
+    # A pipeline whose `seed` is per frame INSIDE a launch (VideoSDPipeline(device_seed=True)) says so: frames that differ only in
+    # `seed` then share a launch, and the launch gets the seeds of its frames as a list, in request order.
+    per_seed = bool(getattr(pipe, "per_frame_seed", False))
+
+    def same_options(a, b):
+        if not per_seed:
+            return a == b
+        return {k: v for k, v in a.items() if k != "seed"} == {k: v for k, v in b.items() if k != "seed"}
+
     backlog, inflight, lane = [], [], 0
     ema_launch_s = [0.0]  # running average: request taken -> launch collected
     stats = _Stats()
@@ -531,6 +540,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
             conn.send((rid, True, snap))
             continue
         group_ = [(rid, args, slot)]
+        seeds_ = [kwargs.get("seed", 42)]  # (`infer`'s default)
         batchable = max_batch > 1 and method == "infer" and len(args) == 1 and hasattr(pipe, "infer_batch")
         if batchable and hasattr(pipe, "can_batch"):
             try:
@@ -551,16 +561,17 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
                     nxt = backlog.pop(0) if backlog else conn.recv()
                 except (EOFError, OSError):
                     nxt = None
-                if nxt is not None and nxt[1] == "infer" and len(nxt[2]) == 1 and nxt[3] == kwargs:
+                if nxt is not None and nxt[1] == "infer" and len(nxt[2]) == 1 and same_options(nxt[3], kwargs):
                     r2, _m, a2, _k, s2 = take(nxt)
                     group_.append((r2, a2, s2))
+                    seeds_.append(_k.get("seed", 42))
                 else:  # different options / another method / shutdown: serve it next, stop growing this batch
                     backlog.insert(0, nxt)
                     break
         if batchable and pipelined:
             # launches in flight run on engines of THEIR plan: anything that re-prepares (other options, another prompt)
             # waits for them (`_engine_for` / `set_text_embeds` under a running graph)
-            if inflight and inflight[-1][3] != kwargs:
+            if inflight and not same_options(inflight[-1][3], kwargs):
                 # another session's frame: other prompts / sizes / step counts run BESIDE what is in flight (own plan, own
                 # prompt constants per lane); only a pipeline that says so (or cannot say) makes it wait
                 if not hasattr(pipe, "needs_idle") or pipe.needs_idle(**kwargs):
@@ -570,7 +581,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
             busy = {e[4] for e in inflight}
             lane = next(l for l in range(lanes) if l not in busy)
             try:
-                handle = pipe.submit_batch([a[0] for _, a, _s in group_], lane=lane, **kwargs)
+                handle = pipe.submit_batch([a[0] for _, a, _s in group_], lane=lane, **(dict(kwargs, seed=list(seeds_)) if per_seed else kwargs))
             except BaseException as e:
                 drain()
                 fail(group_, e)
@@ -582,7 +593,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
         drain()  # anything else runs alone, after what is in flight
         try:
             if len(group_) > 1:
-                outs = pipe.infer_batch([a[0] for _, a, _s in group_], **kwargs)
+                outs = pipe.infer_batch([a[0] for _, a, _s in group_], **(dict(kwargs, seed=list(seeds_)) if per_seed else kwargs))
                 for (r, _a, s), o in zip(group_, outs):
                     reply(r, o, s)
                 stats.add(len(group_), (time.time() - t_in) * 1e3)

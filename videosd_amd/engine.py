@@ -438,6 +438,7 @@ class Engine:
         self.plan = None
         self.graph = None
         self.program = self.program_serial = None
+        self.seed_dev = self._seed_host = None  # `prepare(device_seed=True)`: one seed per frame of the launch, device buffer + pinned mirror
         self.use_graph = True
         self.is_slot = False
         self.batch = 1
@@ -499,6 +500,7 @@ class Engine:
         e.plan = None
         e._stage = None  # own pinned staging buffers and events (a copy of the parent's would be SHARED with it)
         e._raw_stage = None
+        e.seed_dev = e._seed_host = None
         e.pblock = None
         e._installed = None
         e._want = None
@@ -1071,7 +1073,7 @@ class Engine:
 
     def prepare(self, H: int, W: int, steps: int, strength: float, controlnet_scale: float = 1.0,
                 use_controlnet: bool = True, use_graph: Optional[bool] = None, autotune: bool = True, batch: int = 1,
-                ref_mode: bool = False):
+                ref_mode: bool = False, device_seed: bool = False):
         """Fix the frame geometry and schedule; build the static program and capture it into a hipGraph
         (the reference's intent at videopipeline.py:35-47, `compile_model`).
 
@@ -1082,7 +1084,15 @@ class Engine:
         batch > 1: that many frames (of independent streams / sessions, or consecutive frames of one stream) go
         through every kernel together, stacked along the GEMM M dimension: one pass over the 2.45 GB of weights and
         one launch per layer serve all of them.  Each frame is still denoised independently (own GroupNorm statistics,
-        own attention, same noise draws as a lone frame: the reference resets its RNG per frame)."""
+        own attention, same noise draws as a lone frame: the reference resets its RNG per frame).
+
+        device_seed: the noise is drawn on the device, inside the captured program, as a function of one seed PER FRAME of the
+        launch (include/vsd.h THE NOISE CONTRACT; `submit_*(seeds=...)`): the program records vsd_add_noise_seeded /
+        vsd_lcm_step_seeded in place of the `_dev` forms -- launch for launch -- and reads the seeds from `seed_dev`, a buffer of
+        this engine's own; there is no host noise table.  A new seed is 8 bytes per frame copied ahead of the launch: no drain,
+        no `update_options`, no re-capture.  Default: the CPU-contract draws of `host_noise`, the same for every frame."""
+        if device_seed and not all(hasattr(self.ops, f) for f in ("add_noise_seeded", "lcm_step_seeded")):
+            raise ValueError("device_seed=True needs the ops add_noise_seeded and lcm_step_seeded, which this ops object does not have")
         if batch < 1:
             raise ValueError("batch must be >= 1")
         self.batch = batch
@@ -1150,8 +1160,16 @@ class Engine:
         self._cn_scale_consts = c[2 + 6 * n:]
         # noise draws: the reference resets the global CPU generator to a fresh-Generator state on every
         # frame (videopipeline.py:126), so for a fixed shape the draws are the same every frame.
-        draws, ref_draws = self.host_noise(n, h0, w0, ref=ref_mode)
-        self.noise = ops.to_device(draws)
+        draws = ref_draws = None
+        if device_seed:
+            # one seed per frame of the launch, u32 (low, high) pairs = little-endian u64: this engine's own (a slot has its own)
+            self.noise = self.noise_ref = None
+            self.seed_dev = seeds = ops.zeros(B, dtype=torch.int64)
+            self._seed_host = torch.zeros(B, dtype=torch.int64, pin_memory=torch.cuda.is_available())
+        else:
+            self.seed_dev = self._seed_host = None
+            draws, ref_draws = self.host_noise(n, h0, w0, ref=ref_mode)
+            self.noise = ops.to_device(draws)
         a = self.arena
         enc_in = a.alloc(B * H * W, 8)
         x0 = a.alloc(B * hw0, 8)
@@ -1184,7 +1202,8 @@ class Engine:
         if ref_mode:
             ref_b = ops.zeros(1, H, W, 3, dtype=torch.uint8)
             self.ref_u8 = ref_b[0]
-            self.noise_ref = ops.to_device(ref_draws)
+            if not device_seed:
+                self.noise_ref = ops.to_device(ref_draws)
             ref_in, ref_x0, ref_xt, ref_eps = a.alloc(H * W, 8), a.alloc(hw0, 8), a.alloc(hw0, 8), a.alloc(hw0, 8)
             for t in (ref_x0, ref_xt, ref_eps):
                 ops.zero_(t)
@@ -1192,7 +1211,10 @@ class Engine:
             self._encode(r, ref_in, H, W, ref_x0)
             self.buffers["ref_x0"] = ref_x0
         # every frame gets the same draws: the reference resets its RNG per frame
-        r.add_noise_dev(x0, self.noise[0], c[0:2], hw0, B, lat[0])
+        if device_seed:
+            r.add_noise_seeded(x0, seeds, 0, 0, c[0:2], hw0, B, lat[0])
+        else:
+            r.add_noise_dev(x0, self.noise[0], c[0:2], hw0, B, lat[0])
         mark = a.mark()
         for i in range(n):
             a.rewind(mark)
@@ -1230,7 +1252,10 @@ class Engine:
                 rc = RefCtx(self.ucfg)
                 # ref_xt = add_noise(ref latents, fresh draw, t_i) (lcm_reference_pipeline.py:861-871); the coefficients of
                 # timestep t_i are the first two of the step's scheduler coefficients
-                r.add_noise_dev(ref_x0, self.noise_ref[i], c[2 + 6 * i:4 + 6 * i], hw0, 1, ref_xt)
+                if device_seed:  # (kind 1: the reference latents' draws, one per step)
+                    r.add_noise_seeded(ref_x0, seeds, 1, i, c[2 + 6 * i:4 + 6 * i], hw0, 1, ref_xt)
+                else:
+                    r.add_noise_dev(ref_x0, self.noise_ref[i], c[2 + 6 * i:4 + 6 * i], hw0, 1, ref_xt)
                 w_mid, w_skips = self._unet_encoder(r, i, ref_xt, sizes, ref=rc, temb=self.shared["temb"]["ref"])
                 self._unet_decoder(r, i, w_mid, w_skips, sizes, ref_eps, ref=rc, temb=self.shared["temb"]["ref"])
                 rc.mode = "read"
@@ -1238,9 +1263,13 @@ class Engine:
             else:
                 u_mid, u_skips = self._unet_encoder(r, i, cur, sizes)
             self._unet_decoder(r, i, u_mid, u_skips, sizes, eps, ref=rc if ref_mode else None)
-            nz = self.noise[i + 1] if sched.multistep else None
             last = i == n - 1
-            r.lcm_step_dev(eps, cur, nz, c[2 + 6 * i:8 + 6 * i], hw0, B, nxt, den, dec_in if last else None)
+            if device_seed:  # (draw i + 1 = today's noise[i + 1]; 0: a one-step schedule adds none)
+                r.lcm_step_seeded(eps, cur, seeds, 0, i + 1 if sched.multistep else 0, c[2 + 6 * i:8 + 6 * i], hw0, B, nxt, den,
+                                  dec_in if last else None)
+            else:
+                nz = self.noise[i + 1] if sched.multistep else None
+                r.lcm_step_dev(eps, cur, nz, c[2 + 6 * i:8 + 6 * i], hw0, B, nxt, den, dec_in if last else None)
         self._decode(r, dec_in, h0, w0, dec_out)
         r.postprocess_rgb(dec_out, 8, B * H * W, out_b)
         # program: what a lone launch runs (the ControlNet encoder on the side stream when `overlap_controlnet`);
@@ -1248,7 +1277,7 @@ class Engine:
         self.program = r.flavor(0 if self.overlap_controlnet or not self._twin_now else 1)
         self.program_serial = r.flavor(1) if self._twin_now and self.overlap_controlnet and use_controlnet else self.program
         self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=n, batch=B,
-                         ref_mode=bool(ref_mode), tuned_for_lanes=bool(self.tune_for_lanes),
+                         ref_mode=bool(ref_mode), device_seed=bool(device_seed), tuned_for_lanes=bool(self.tune_for_lanes),
                          sizes=sizes, timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=a.peak)
         # per-shape kernel configuration (timed once per shape, cached in ops.tile_override), warm-up, capture
         torch.cuda.synchronize() if torch.cuda.is_available() else None  # allocation fills vs. kernel streams
@@ -1512,12 +1541,33 @@ class Engine:
             self._stage = st
         return st
 
-    def submit_u8(self, frame: np.ndarray, overlap: Optional[bool] = None):
+    def _check_seeds(self, seeds):
+        """`seeds=` of a submit -> None (keep the seeds in place) or a list of B ints, refused BEFORE anything is enqueued"""
+        if seeds is None:
+            return None
+        if self.seed_dev is None:
+            raise ValueError("seeds= needs an engine prepared with device_seed=True (the default noise does not depend on a seed)")
+        B = self.plan["batch"]
+        vals = [seeds] * B if isinstance(seeds, (int, np.integer)) else list(seeds)
+        if len(vals) != B or not all(isinstance(v, (int, np.integer)) for v in vals):
+            raise ValueError(f"seeds must be an int or a sequence of {B} ints (one per frame of the launch)")
+        return [int(v) & 0xFFFFFFFFFFFFFFFF for v in vals]
+
+    def _upload_seeds(self, vals):
+        """the launch's seeds (`_check_seeds`) on the lane's stream ahead of the graph launch, like the frame upload: 8 bytes per
+        frame from the pinned mirror (the lane's previous launch has been collected, so nothing in flight reads the mirror)"""
+        if vals is not None:
+            self._seed_host.numpy().view(np.uint64)[:] = np.array(vals, dtype=np.uint64)
+            self.ops.upload(self.seed_dev, self._seed_host)
+
+    def submit_u8(self, frame: np.ndarray, overlap: Optional[bool] = None, seeds=None):
         """Upload + enqueue one frame (or batch) without waiting: pair with `collect_u8`.  Lets the host prepare the
-        next frames / post-process the previous ones while this one is on the GPU.  overlap: see `launch`."""
+        next frames / post-process the previous ones while this one is on the GPU.  overlap: see `launch`.
+        seeds (device_seed engines): an int, or one int per frame of the launch; None keeps the seeds of the launch before."""
         want = self._want_shape()
         if frame.shape != want or frame.dtype != np.uint8:
             raise ValueError(f"frame must be uint8 {want}, got {frame.dtype} {frame.shape}")
+        self._upload_seeds(self._check_seeds(seeds))
         _, hin, _hout, e0, e1 = self._staging()
         hin.numpy()[...] = frame.reshape(hin.shape)
         self.ops.upload(self.frame_u8, hin)
@@ -1537,12 +1587,13 @@ class Engine:
             self._raw_stage = st
         return st
 
-    def submit_raw_u8(self, frame, overlap: Optional[bool] = None):
+    def submit_raw_u8(self, frame, overlap: Optional[bool] = None, seeds=None):
         """`submit_u8` for CAMERA frames: uint8 [h][w][3] of any size (prepared with batch B > 1: a list of B frames, possibly of
         different sizes).  The reference's centre crop + LANCZOS resize (videopipeline.py:92-107) runs on the device: the crop box
         alone is uploaded and resampled into `frame_u8` by an ordinary launch in front of the captured program, bit for bit what
-        PIL gives on the host.  A frame already of the plan's size goes straight into `frame_u8`."""
+        PIL gives on the host.  A frame already of the plan's size goes straight into `frame_u8`.  seeds: see `submit_u8`."""
         p = self.plan
+        seeds = self._check_seeds(seeds)
         H, W, B = p["H"], p["W"], p["batch"]
         frames = [frame] if B == 1 and isinstance(frame, np.ndarray) else list(frame)
         if len(frames) != B:
@@ -1558,6 +1609,7 @@ class Engine:
             total += _ru((r - l) * (b - t) * 3, 256)
         hraw, draw = self._raw_staging(total)
         _, _hin, _hout, e0, e1 = self._staging()
+        self._upload_seeds(seeds)
         for i, (f, (l, t, r, b, off)) in enumerate(zip(frames, boxes)):
             bw, bh = r - l, b - t
             n = bw * bh * 3
@@ -1579,16 +1631,17 @@ class Engine:
         self.submit_raw_u8(frame)
         return self.collect_u8()
 
-    def submit_raw_i420(self, frame, overlap: Optional[bool] = None):
+    def submit_raw_i420(self, frame, overlap: Optional[bool] = None, seeds=None):
         """`submit_raw_u8` for planar YUV 4:2:0 camera frames (`frames.I420Frame`, any size, odd sizes included; prepared with batch
         B > 1: a list of B frames, possibly of different sizes).  Per frame: the reference's crop box on the full frame size, widened
         to an even left / top edge so that it starts on a chroma sample; only those plane rectangles are copied into the pinned
         staging and uploaded (1.5 bytes per pixel); `i420_to_rgb` into device scratch (straight into `frame_u8` when the box already
         has the plan's size), `resample_rgb` of the box inside that rectangle into `frame_u8`; then `launch`.  The bytes of "convert
-        the whole frame by the colour contract (include/vsd.h), crop, LANCZOS-resize with PIL"."""
+        the whole frame by the colour contract (include/vsd.h), crop, LANCZOS-resize with PIL".  seeds: see `submit_u8`."""
         from .frames import I420Frame
 
         p = self.plan
+        seeds = self._check_seeds(seeds)
         H, W, B = p["H"], p["W"], p["batch"]
         frames = [frame] if B == 1 and isinstance(frame, I420Frame) else list(frame)
         if len(frames) != B:
@@ -1611,6 +1664,7 @@ class Engine:
         hraw, draw = self._raw_staging(total)
         rgb = self.ops.workspace("i420_rgb", scratch) if scratch else None
         _, _hin, _hout, e0, e1 = self._staging()
+        self._upload_seeds(seeds)
         hb = hraw.numpy()
         for i, (f, (l, t, r, b, el, et, rw, rh, cw, ch, ys, cs, off)) in enumerate(zip(frames, rects)):
             ou, ov = off + ys * rh, off + ys * rh + cs * ch

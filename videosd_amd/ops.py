@@ -993,6 +993,22 @@ class HipOps:
         self.ctx.call("vsd_lcm_step_dev", self._p(eps), self._p(sample), self._p(noise_f32), self._p(coef_dev), hw, batch,
                       self._p(prev), self._p(denoised), self._p(dec_in), self.s)
 
+    # ---- seeded noise (include/vsd.h THE NOISE CONTRACT; csrc/noise.hip)
+    def noise_fill(self, seed: int, kind: int, draw: int, hw: int, out, raw: bool = False):
+        """one draw of `hw` latent pixels for `seed` (any int, taken modulo 2^64): fp32 [4][hw], or raw=True the Philox integers u32 [hw][4]"""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.ctx.call("vsd_noise_fill", seed & 0xFFFFFFFF, seed >> 32, int(kind), int(draw), hw, int(bool(raw)), self._p(out), self.s)
+
+    def add_noise_seeded(self, x0, seeds_dev, kind, draw, coef_dev, hw, batch, out):
+        """`add_noise_dev` with the draw computed in the kernel; seeds_dev: u32 [batch][2] (low, high) in device memory"""
+        self.ctx.call("vsd_add_noise_seeded", self._p(x0), self._p(seeds_dev), int(kind), int(draw), self._p(coef_dev), hw, batch,
+                      self._p(out), self.s)
+
+    def lcm_step_seeded(self, eps, sample, seeds_dev, kind, draw, coef_dev, hw, batch, prev, denoised, dec_in=None):
+        """`lcm_step_dev` with the draw computed in the kernel; draw <= 0: the step adds no noise"""
+        self.ctx.call("vsd_lcm_step_seeded", self._p(eps), self._p(sample), self._p(seeds_dev), int(kind), int(draw), self._p(coef_dev),
+                      hw, batch, self._p(prev), self._p(denoised), self._p(dec_in), self.s)
+
     def adain(self, x, stats, stats_ref, rows, c, out, eps=1e-6):
         """reference-only AdaIN: per-channel re-normalisation of x to the banked statistics (fp32 [c][2] sum / sumsq)"""
         self.ctx.call("vsd_adain", self._p(x), self._p(stats), self._p(stats_ref), rows, c, eps, self._p(out), self.s)

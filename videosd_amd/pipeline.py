@@ -52,6 +52,8 @@ def load_or_synthesize(spec, prefix: str, filename: str, device, snapshot_file: 
         return w, path
     return W.synthesize(spec, prefix, device=device), "synthetic"
 
+_DEVICE_SEED = ("device_seed", True)  # the element a plan key ends with in that mode (no prompt key of an SDXL plan looks like it)
+
 
 class VideoSDPipeline:
     """One instance = one GPU = one full weight replica (the reference's Ray actor with num_gpus=1)."""
@@ -69,6 +71,13 @@ class VideoSDPipeline:
         # frame (videopipeline.py:92-107) runs on the GPU instead of in PIL on this host thread -- the same bytes (csrc/resample.hip).
         # RGB frames whose target size is a multiple of 8 take it; everything else keeps the host path.
         self.device_resize = bool(kwargs.get("device_resize", False))
+        # extension, off by default: `seed` changes the picture.  The noise of every frame is drawn on the device from ITS seed
+        # (include/vsd.h THE NOISE CONTRACT; Engine.prepare(device_seed=True)); `infer_batch` / `submit_batch` take one seed per
+        # frame, and a worker coalesces frames that differ only in `seed` (`per_frame_seed`, read by dispatch.py).  Off: the
+        # reference's CPU-contract draws, the same for every frame and seed.
+        self.device_seed = bool(kwargs.get("device_seed", False))
+        if self.device_seed:
+            self.per_frame_seed = True
         # launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on
         # launch stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch
         self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
@@ -340,7 +349,8 @@ class VideoSDPipeline:
     ):
         """Same contract as videopipeline.py:75-128.  `guidance_scale`, `ref`, `style_fidelity` and
         `controlnet` are accepted and ignored exactly like the reference (ControlNet always runs; 7.5 is baked
-        in); `seed` does not change the result because the reference resets the CPU generator state per frame."""
+        in); `seed` does not change the result because the reference resets the CPU generator state per frame -- unless the
+        object was built with `device_seed=True`: then the frame's noise is a function of `seed` (include/vsd.h)."""
         return self.infer_batch([img], prompt=prompt, height=height, width=width, strength=strength, steps=steps,
                                 guidance_scale=guidance_scale, ref=ref, style_fidelity=style_fidelity,
                                 controlnet=controlnet, seed=seed, controlnet_scale=controlnet_scale)[0]
@@ -421,7 +431,13 @@ class VideoSDPipeline:
 
         n_eff = len(lcm_timesteps(float(strength), int(steps)))  # ValueError for an empty schedule: the caller's problem
         # (SDXL: the pooled text embedding is baked into the time embeddings at `prepare`, so the prompt is part of the program)
-        plan_key = (height, width, int(steps), n_eff, use_cn, use_ref) + ((pkey,) if self.is_xl else ())
+        plan_key = (height, width, int(steps), n_eff, use_cn, use_ref) + ((pkey,) if self.is_xl else ()) + ((_DEVICE_SEED,) if getattr(self, "device_seed", False) else ())
+        seeds = None
+        if getattr(self, "device_seed", False):
+            seeds = [seed] * len(imgs) if isinstance(seed, (int, np.integer)) else list(seed)
+            if len(seeds) != len(imgs) or not all(isinstance(v, (int, np.integer)) for v in seeds):
+                raise ValueError(f"seed must be an int or a sequence of {len(imgs)} ints (one per frame)")
+            seeds = [int(v) for v in seeds]
         opts = (float(strength), float(controlnet_scale))
         eng = self._engine_for(plan_key, opts, len(imgs), lane, prompt=pblock, prompt_text=prompt)
         eng.use_prompt(pblock)  # this lane's launch reads ITS copy of the constants: the other lanes may run other prompts
@@ -429,17 +445,18 @@ class VideoSDPipeline:
             rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), width, height), dtype=np.uint8)
             eng.ops.upload(eng.ref_u8, torch.from_numpy(np.array(rf, copy=True)))  # (PIL's buffer is read-only)
             eng._ref_epoch = self._ref_epoch
-        np.random.seed(seed)  # kept for parity with videopipeline.py:112 (nothing downstream consumes it)
+        np.random.seed(seed if seeds is None else seeds[0] & 0xFFFFFFFF)  # kept for parity with videopipeline.py:112 (nothing downstream consumes it)
         t0 = time.perf_counter()
+        skw = {} if seeds is None else {"seeds": seeds}  # (engines of the default mode, and stand-ins, are called as before)
         if i420 is not None:
-            eng.submit_raw_i420(i420[0] if len(i420) == 1 else i420, overlap=self._overlap_now(lane))
+            eng.submit_raw_i420(i420[0] if len(i420) == 1 else i420, overlap=self._overlap_now(lane), **skw)
             up = eng.last_upload_bytes
         elif raw is not None:
-            eng.submit_raw_u8(raw[0] if len(raw) == 1 else raw, overlap=self._overlap_now(lane))
+            eng.submit_raw_u8(raw[0] if len(raw) == 1 else raw, overlap=self._overlap_now(lane), **skw)
             up = sum((b[2] - b[0]) * (b[3] - b[1]) * 3 for b in (eng.ops.center_crop_box(f.shape[1], f.shape[0], width, height) for f in raw))
         else:
             frames = np.stack([np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8) for im in imgs])
-            eng.submit_u8(frames[0] if len(imgs) == 1 else frames, overlap=self._overlap_now(lane))
+            eng.submit_u8(frames[0] if len(imgs) == 1 else frames, overlap=self._overlap_now(lane), **skw)
             up = frames.nbytes
         self._io_bytes["up"] = up // len(imgs)  # bytes handed to the host-to-device copy per frame of this launch (counted, not timed)
         self._outstanding.append(eng)
@@ -543,6 +560,8 @@ class VideoSDPipeline:
             pk = (o["height"] - o["height"] % 8, o["width"] - o["width"] % 8, int(o["steps"]), n_eff, use_cn and not use_ref, use_ref)
             if self.is_xl:
                 pk += (o["prompt"] if isinstance(o["prompt"], str) else tuple(o["prompt"]),)
+            if getattr(self, "device_seed", False):
+                pk += (_DEVICE_SEED,)
             plan = self._plans.get(pk)
             if plan is None:
                 return False
@@ -597,8 +616,9 @@ class VideoSDPipeline:
         # with four lanes busy; one-frame launches and workers with one or two lanes are the latency case -- the forms that are
         # fastest alone.  Fixed per plan, the same on every lane (same bits whichever lane a frame lands on).
         eng.tune_for_lanes = self.max_lanes >= 3 and batch > 1
+        mode = {"device_seed": True} if _DEVICE_SEED in plan_key[6:] else {}
         eng.prepare(height, width, steps, strength, controlnet_scale=cn_scale, use_controlnet=use_cn, batch=batch, ref_mode=use_ref,
-                    autotune=self.tuning_mode != "table")
+                    autotune=self.tuning_mode != "table", **mode)
         eng._ref_epoch = None
         plan["engines"][(batch, lane)] = eng
         self._note("prepare", t0)

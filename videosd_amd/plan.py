@@ -10,7 +10,9 @@ under stream capture and keeps the graph; `vsd_plan_infer` is upload, launch, do
 produces is bit for bit the engine's (tests/test_plan_gpu.py).
 
 A plan is one (size, steps, frames per launch): prompt (`export_prompt` / vsd_plan_load_prompt), strength and ControlNet scale
-(vsd_plan_set_options) change on the loaded plan.
+(vsd_plan_set_options) change on the loaded plan -- and, for an engine prepared with device_seed, the seed of every frame of a launch
+(vsd_plan_set_seeds).  That needs no field in the file: the loader finds the seed buffer as the `seeds_dev` argument of the program's
+vsd_add_noise_seeded call, a region of the plan's own like every other constant.
 
 LIVE OPTIONS.  Three things in a prepared program depend on strength / controlnet_scale, all written by Engine._write_constants: the
 fp32 constant block, and per network the per-step time-embedding table.  LCM timesteps take only the 50 values 19, 39, ... 999, so
@@ -63,7 +65,9 @@ OTHER_PROGRAM = 1         # include/vsd.h VSD_PLAN_OTHER_PROGRAM
 # entry points a frame program may call, by id (csrc/plan_dispatch.inc is generated from this list: scripts/gen_plan_dispatch.py)
 PLAN_FUNCS = ["vsd_preprocess_rgb", "vsd_sobel_control", "vsd_conv_gemm", "vsd_conv_gemm_group", "vsd_pair_begin", "vsd_pair_join",
               "vsd_pair_end", "vsd_groupnorm", "vsd_groupnorm_batched", "vsd_attention", "vsd_attention_batched", "vsd_tail_a", "vsd_tail_b",
-              "vsd_add_noise_dev", "vsd_lcm_step_dev", "vsd_postprocess_rgb", "vsd_adain", "vsd_layernorm"]
+              "vsd_add_noise_dev", "vsd_lcm_step_dev", "vsd_postprocess_rgb", "vsd_adain", "vsd_layernorm",
+              # (new entry points go to the END: the ids of the ones above are in every plan file written so far)
+              "vsd_add_noise_seeded", "vsd_lcm_step_seeded"]
 T_I32, T_F32, T_PTR, T_NULL, T_STREAM, T_DESC = range(6)
 
 
@@ -315,7 +319,7 @@ def export_plan(engine, path: str) -> dict:
     assert len(opts) == OPT_FIXED_BYTES + OPT_TABLE_BYTES * len(tables)
     ext = struct.pack("<IQ", L.VERSION, signature_hash()) + opts
     # what may be shared between lanes: allocations that hold a network's weight tensor -- and are nothing the program writes
-    private = [engine.pblock.buf, consts, coef_dev, engine.noise, engine.frame_u8, engine.out_u8, engine.edge_u8, getattr(engine, "noise_ref", None),
+    private = [engine.pblock.buf, consts, coef_dev, engine.noise, getattr(engine, "seed_dev", None), engine.frame_u8, engine.out_u8, engine.edge_u8, getattr(engine, "noise_ref", None),
                getattr(engine, "ref_u8", None)] + [t for _, live, table in tables for t in (live, table)] + list(engine.shared["temb"].values())
     never = {regs.find(t.untyped_storage().data_ptr()) for t in private if t is not None} | {regs.find(s) for s in scratch}
     seen = set()
@@ -431,6 +435,13 @@ class CPlan:
             return False
         self.ctx.check(rc, "vsd_plan_set_options")
         return True
+
+    def set_seeds(self, seeds):
+        """vsd_plan_set_seeds: one seed per frame of the launch (an int: the same for all) for the frames submitted from now on --
+        stream-ordered, no re-capture.  Only a plan exported from an engine prepared with device_seed has seeds."""
+        vals = [seeds] * self.batch if isinstance(seeds, (int, np.integer)) else list(seeds)
+        arr = (C.c_uint64 * len(vals))(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in vals])
+        self.ctx.call("vsd_plan_set_seeds", self.h, arr, len(vals))
 
     def clone(self, lane: int = -1) -> "CPlan":
         """vsd_plan_clone_lane: a further plan of this program on launch stream `lane` that shares this one's weights; it starts with
