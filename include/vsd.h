@@ -52,7 +52,7 @@ enum vsd_family {
   VSD_FAM_ATTENTION = 4, VSD_FAM_ELEMENTWISE = 5, VSD_FAM_COUNT = 6
 };
 
-/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds) and the size in
+/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds; vsd_prompt_install joined version 10 without a bump: plan files do not change, and a library without the symbol is refused by name at load) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
 #define VSD_VERSION 10
@@ -277,6 +277,28 @@ int vsd_add_noise_seeded(vsd_ctx* ctx, const void* x0, const void* seeds_dev, in
                          void* out, void* stream);
 int vsd_lcm_step_seeded(vsd_ctx* ctx, const void* eps, const void* sample, const void* seeds_dev, int kind, int draw, const void* coef_dev,
                         int hw, int batch, void* prev, void* denoised, void* dec_in, void* stream);
+
+/* ---- per-frame prompts: one cached prompt into a frame slot (csrc/prompt_install.hip) ---------------------------------------------------
+ * A launch whose frames have prompts of their own (Engine.prepare with frame_prompts) reads the cross-attention constants of every
+ * BasicTransformerBlock from a PER-FRAME block: K as fp16 [B*tl][c], frame b owning rows [b*tl, (b+1)*tl), and V^T as fp16 [c][B*ldt],
+ * ldt = round_up(tl, 64), frame b owning columns [b*ldt, (b+1)*ldt), zero beyond its tl keys -- what vsd_attention_batched takes with
+ * k_batch_rows = tl, vt_batch_cols = ldt.  A prompt cache entry holds ONE prompt's K [tl][c] and V^T [c][ldt].  vsd_prompt_install copies
+ * such an entry (src_block) into slot `frame` of a per-frame block (dst_block) in ONE launch on `stream`, ahead of the captured program:
+ * nothing is re-captured, nothing waits.  src_block must stay allocated and unchanged until the launch has executed.
+ * segs_dev: nseg segments in DEVICE memory (16-byte aligned), built once per pair of layouts.  Segment i copies `rows` rows of
+ *   `row_bytes` bytes, dense in the source from byte src_off on, to dst_off + frame * dst_frame_stride + row * dst_pitch.  Every field but
+ *   the count `rows` is in bytes and a multiple of 16; rows >= 1; dst_pitch is the same whole number B of dst_frame_stride in every
+ *   segment (the destination's frame slots), dst_frame_stride >= row_bytes.  A K segment is one run (rows = 1, row_bytes =
+ *   dst_frame_stride = tl*c*2, dst_pitch = B*tl*c*2); a V^T segment is c rows of ldt*2 bytes at pitch B*ldt*2 -- all ldt columns, so that
+ *   the zero padding travels with the data.  16-byte vector loads and stores, a row's chunks on consecutive lanes.
+ * A table is read back and checked when the context first sees it (one blocking copy; the engine's prepare), and must not change
+ * afterwards; nseg = 0 makes the context forget the table at segs_dev (before its memory is reused; the other arguments are ignored).
+ * VSD_ERR_ARG with a reason: a misaligned pointer or field, frame outside [0, B), nseg outside [0, 65535].  The destination's SIZE is the
+ * caller's: the largest dst_off + (rows - 1) * dst_pitch + B * dst_frame_stride must lie inside dst_block. */
+typedef struct vsd_prompt_seg {
+  int64_t src_off, dst_off, rows, row_bytes, dst_pitch, dst_frame_stride;
+} vsd_prompt_seg;
+int vsd_prompt_install(vsd_ctx* ctx, const void* src_block, void* dst_block, const vsd_prompt_seg* segs_dev, int nseg, int frame, void* stream);
 
 /* AdaIN of the reference-only mode (lcm_reference_pipeline.py:593-603, dead at v2 but still exposed as `ref`):
  * out[r][c] = (x[r][c] - mean_c) / std_c * std_ref_c + mean_ref_c, statistics over the `rows` pixels of one image,

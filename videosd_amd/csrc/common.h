@@ -7,6 +7,8 @@
 #include <string.h>
 #include <string>
 #include <type_traits>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/vsd.h"
@@ -55,6 +57,7 @@ struct vsd_ctx {
   int num_cus = 256;          // compute units of the device (grid of the persistent kernels)
   double fam_flops[VSD_FAM_COUNT];
   int64_t fam_launch[VSD_FAM_COUNT];
+  std::unordered_map<const void*, std::pair<int, int>> prompt_tables;  // vsd_prompt_install: table -> (segments, frame slots), once checked
 };
 
 static inline int vsd_fail(vsd_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

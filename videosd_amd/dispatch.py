@@ -329,10 +329,25 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
     # `seed` then share a launch, and the launch gets the seeds of its frames as a list, in request order.
     per_seed = bool(getattr(pipe, "per_frame_seed", False))
 
+    # ... and one whose PROMPT is per frame inside a launch (VideoSDPipeline(frame_prompts=True)) likewise: frames of sessions that differ in
+    # `prompt` share a launch, which gets `prompts`, one per frame in request order (`prompt` stays the first request's).
+    per_prompt = bool(getattr(pipe, "per_frame_prompt", False))
+    per_frame = tuple(k for k, on in (("seed", per_seed), ("prompt", per_prompt)) if on)
+
     def same_options(a, b):
-        if not per_seed:
+        if not per_frame:
             return a == b
-        return {k: v for k, v in a.items() if k != "seed"} == {k: v for k, v in b.items() if k != "seed"}
+        return {k: v for k, v in a.items() if k not in per_frame} == {k: v for k, v in b.items() if k not in per_frame}
+
+    def launch_options(kwargs, seeds, prompts):
+        if not per_frame:
+            return kwargs
+        kw = dict(kwargs)
+        if per_seed:
+            kw["seed"] = list(seeds)
+        if per_prompt:
+            kw["prompts"] = list(prompts)
+        return kw
 
     backlog, inflight, lane = [], [], 0
     ema_launch_s = [0.0]  # running average: request taken -> launch collected
@@ -541,6 +556,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
             continue
         group_ = [(rid, args, slot)]
         seeds_ = [kwargs.get("seed", 42)]  # (`infer`'s default)
+        prompts_ = [kwargs.get("prompt", ["pixar, cg"])]  # (likewise)
         batchable = max_batch > 1 and method == "infer" and len(args) == 1 and hasattr(pipe, "infer_batch")
         if batchable and hasattr(pipe, "can_batch"):
             try:
@@ -565,6 +581,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
                     r2, _m, a2, _k, s2 = take(nxt)
                     group_.append((r2, a2, s2))
                     seeds_.append(_k.get("seed", 42))
+                    prompts_.append(_k.get("prompt", ["pixar, cg"]))
                 else:  # different options / another method / shutdown: serve it next, stop growing this batch
                     backlog.insert(0, nxt)
                     break
@@ -581,7 +598,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
             busy = {e[4] for e in inflight}
             lane = next(l for l in range(lanes) if l not in busy)
             try:
-                handle = pipe.submit_batch([a[0] for _, a, _s in group_], lane=lane, **(dict(kwargs, seed=list(seeds_)) if per_seed else kwargs))
+                handle = pipe.submit_batch([a[0] for _, a, _s in group_], lane=lane, **launch_options(kwargs, seeds_, prompts_))
             except BaseException as e:
                 drain()
                 fail(group_, e)
@@ -593,7 +610,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
         drain()  # anything else runs alone, after what is in flight
         try:
             if len(group_) > 1:
-                outs = pipe.infer_batch([a[0] for _, a, _s in group_], **(dict(kwargs, seed=list(seeds_)) if per_seed else kwargs))
+                outs = pipe.infer_batch([a[0] for _, a, _s in group_], **launch_options(kwargs, seeds_, prompts_))
                 for (r, _a, s), o in zip(group_, outs):
                     reply(r, o, s)
                 stats.add(len(group_), (time.time() - t_in) * 1e3)

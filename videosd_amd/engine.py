@@ -364,6 +364,47 @@ class PromptLayout:
         self.nbytes = max(off, 256)
 
 
+class FramePromptLayout:
+    """Byte layout of the cross-attention constants of a launch whose B frames have prompts of their OWN (`Engine.prepare(frame_prompts=True)`):
+    per BasicTransformerBlock K as [B*tl][C], frame b owning rows [b*tl, (b+1)*tl), and V^T as [C][B*ldt], frame b owning columns
+    [b*ldt, (b+1)*ldt) with zeros beyond its tl keys -- what `attention(batch=B, k_brows=tl, vt_bcols=ldt)` reads.  No absorbed weights: they
+    would be per frame too (B weight sets per layer), so every cross-attention of such a program runs in the explicit form."""
+
+    def __init__(self, nets, tl: int, frames: int):
+        self.tl, self.ldt, self.frames = tl, _ru(tl, 64), int(frames)
+        self.items = {}
+        self.absorbed = frozenset()
+        off = 0
+        for ni, net in enumerate(nets):
+            for bi, t in enumerate(net.transformers):
+                c = t.kv2.n // 2
+                if c % 8:
+                    raise ValueError(f"frame_prompts: a {c}-wide transformer block: rows must be whole 16-byte chunks (C a multiple of 8)")
+                for name, shape in (("k", (self.frames * tl, c)), ("vt", (c, self.frames * self.ldt))):
+                    self.items[(ni, bi, name)] = (off, shape, torch.float16)
+                    off = _ru(off + shape[0] * shape[1] * 2, 256)
+        self.nbytes = max(off, 256)
+
+
+def prompt_segments(src: PromptLayout, dst: FramePromptLayout):
+    """The copy list of `vsd_prompt_install` (include/vsd.h vsd_prompt_seg) that puts a cache entry of layout `src` into ONE frame slot of a
+    block of layout `dst`: per tensor (src_off, dst_off, rows, row_bytes, dst_pitch, dst_frame_stride), bytes except the count `rows`.
+    K is one run; V^T is C rows of ALL ldt columns (the zero padding travels with the data) at the destination's pitch."""
+    if src.tl != dst.tl:
+        raise ValueError(f"a prompt of {src.tl} tokens into a per-frame block of {dst.tl}: all frames of a launch must have the same text length")
+    B, segs = dst.frames, []
+    for key, (doff, _dshape, _dt) in dst.items.items():
+        soff, sshape, _st = src.items[key]
+        if key[2] == "k":
+            n = sshape[0] * sshape[1] * 2
+            segs.append((soff, doff, 1, n, B * n, n))
+        else:
+            c, ldt = sshape
+            segs.append((soff, doff, c, ldt * 2, B * ldt * 2, ldt * 2))
+    assert all(v % 16 == 0 for sg in segs for v in sg[:2] + sg[3:])
+    return segs
+
+
 class PromptBlock:
     """One prompt's constants in device memory (layout: PromptLayout).  Engines read THEIR OWN block (its addresses are in
     their captured graphs); a cached prompt is installed by copying its block over the engine's."""
@@ -470,6 +511,10 @@ class Engine:
         self.pblock = None      # this engine's own prompt constants (the addresses its program / graph reads)
         self._installed = None  # the PromptBlock whose bytes `pblock` currently holds
         self._want = None       # `use_prompt`: this engine's prompt (None: the family default)
+        # `prepare(frame_prompts=True)`: `pblock` is a per-frame block (FramePromptLayout) instead
+        self.frame_prompts = False
+        self._want_list = None  # `use_prompts`: one PromptBlock per frame of the launch (None: `_want` / the default for every frame)
+        self._slot_src = []     # the PromptBlock whose K / V^T each frame slot of `pblock` holds (a reference: the source outlives its install)
         self.absorb_cross_attention = True  # cross-attention of the wide blocks as two GEMMs (vsd_xattn_fold)
         self.use_fused_tail = True          # 320-wide blocks: per-token chains as fused launches (csrc/fused_tail.hip)
         self.group_merges = not __import__("os").environ.get("VSD_NO_GROUP")  # the ControlNet merges of a step as two grouped launches
@@ -504,6 +549,8 @@ class Engine:
         e.pblock = None
         e._installed = None
         e._want = None
+        e._want_list = None
+        e._slot_src = []
         e.is_slot = bool(share_plan)
         if not share_plan:
             e.shared = {}
@@ -558,8 +605,52 @@ class Engine:
         the other engines of the family run; None: follow the family default again.  Call it with no launch of THIS engine
         in flight (the other lanes are not affected: every engine reads its own copy)."""
         self._want = blk
+        self._want_list = None
+
+    def use_prompts(self, blks):
+        """`frame_prompts` engines: frame i of this engine's launches uses blks[i] (one `build_prompt` result per frame of the launch, e.g.
+        prompt cache entries; the same object may appear several times) from the next launch on.  Only the frame slots whose entry
+        changed since this engine's last launch are rewritten, each by one `prompt_install` launch on the engine's own stream ahead of the
+        program: nothing is re-captured, nobody waits.  Call it with no launch of THIS engine in flight."""
+        self._want_list = list(blks)
+        self._want = None
+
+    def _frame_sources(self, batch: int):
+        """frame_prompts: the PromptBlock of every frame of a launch of `batch` frames, checked (count, one text length)"""
+        want = getattr(self, "_want_list", None)
+        if want is None:
+            d = self._want if self._want is not None else self.family.get("prompt")
+            if d is None:
+                raise RuntimeError("set_text_embeds (or use_prompt / use_prompts) must be called before a launch")
+            want = [d] * batch
+        if len(want) != batch:
+            raise ValueError(f"use_prompts: {len(want)} prompt(s) for a launch of {batch} frame(s)")
+        if any(b.layout.tl != want[0].layout.tl for b in want):
+            raise ValueError(f"all frames of a launch must have the same text length, got {[b.layout.tl for b in want]}")
+        return want
+
+    def _seg_table(self, src: PromptLayout, dst: FramePromptLayout):
+        """(device table, segments) of `prompt_install` for this pair of layouts: built once per family"""
+        tabs = self.family.setdefault("seg_tables", {})
+        got = tabs.get((src, dst))
+        if got is None:
+            segs = prompt_segments(src, dst)
+            got = tabs[(src, dst)] = (self.ops.to_device(torch.tensor(segs, dtype=torch.int64)), len(segs))
+            self.ops.synchronize()  # (the other lanes' streams read it too)
+        return got
 
     def _sync_prompt(self):
+        if getattr(self, "frame_prompts", False):
+            want = self._frame_sources(self.batch)
+            lay = self.pblock.layout
+            if want[0].layout.tl != lay.tl:
+                raise ValueError(f"the prompts' text length ({want[0].layout.tl}) differs from the one this plan was prepared for ({lay.tl}): prepare again")
+            for f, src in enumerate(want):
+                if src is not self._slot_src[f]:
+                    tab, nseg = self._seg_table(src.layout, lay)
+                    self.ops.prompt_install(src.buf, self.pblock.buf, tab, nseg, f)
+                    self._slot_src[f] = src
+            return
         src = self._want if self._want is not None else self.family.get("prompt")
         if src is None:
             raise RuntimeError("set_text_embeds (or use_prompt) must be called before a launch")
@@ -696,7 +787,7 @@ class Engine:
                     r.attention(qk, 2 * c, qk_full[:, c:], 2 * c, vt_full, ld2, att, c, hw, 2 * hw, heads, d, d ** -0.5)
             ni = 1 if net is self.cn else 0
             kt, vtt = self.pblock.kv(ni, bw.kv_index)
-            xa = self.pblock.xa(ni, bw.kv_index) if self.absorb_cross_attention else None
+            xa = self.pblock.xa(ni, bw.kv_index) if self.absorb_cross_attention else None  # (a per-frame block has none: explicit form)
             fused = (self.use_fused_tail and c == getattr(self.ops, "TAIL_C", 0) and len(tw.blocks) == 1 and ref is None and
                      stat_out is None and out2 is None and hasattr(self.ops, "tail_a"))
             if fused:
@@ -709,7 +800,7 @@ class Engine:
                 h1 = a.alloc(rows, c)
                 q = a.alloc(rows, c)
                 r.tail_a(att, h, rows, bw.out1, bw.q2, h1, q)
-                r.attention(q, c, kt, c, vtt, vtt.shape[1], att, c, rows, kt.shape[0], heads, d, d ** -0.5)
+                self._cross_attention(r, q, kt, vtt, att, c, hw, heads, d)
                 if rows >= self.tail_b_min_rows:
                     out = a.alloc(rows, c)
                     r.tail_b(att, h1, x, rows, bw.out2, bw.ff1, bw.ff2, tw.proj_out, out)
@@ -738,7 +829,7 @@ class Engine:
             else:
                 q = a.alloc(rows, c)
                 r.conv(h1, None, lin, bw.q2, q, ln_part=rs1)
-                r.attention(q, c, kt, c, vtt, vtt.shape[1], att, c, rows, kt.shape[0], heads, d, d ** -0.5)
+                self._cross_attention(r, q, kt, vtt, att, c, hw, heads, d)
                 r.conv(att, None, lin, bw.out2, h2, residual=h1, rowstat_out=rs2)
             # GEGLU feed-forward
             f = a.alloc(rows, 4 * c)
@@ -752,6 +843,16 @@ class Engine:
         r.conv(h, None, lin, tw.proj_out, out, residual=x, out2=out2, add2=add2,
                chanstat_out=stat_out)
         return out
+
+    def _cross_attention(self, r, q, kt, vtt, att, c, hw, heads, d):
+        """q [B*hw][c] over the text's K / V^T: shared by all images of the launch (the queries are one problem of B*hw rows), or -- a
+        per-frame block -- image b over ITS rows of K and columns of V^T (one problem per image, as self-attention)"""
+        if self.frame_prompts:
+            lay = self.pblock.layout
+            r.attention(q, c, kt, c, vtt, vtt.shape[1], att, c, hw, lay.tl, heads, d, d ** -0.5, batch=self.batch, k_brows=lay.tl,
+                        vt_bcols=lay.ldt)
+        else:
+            r.attention(q, c, kt, c, vtt, vtt.shape[1], att, c, self.batch * hw, kt.shape[0], heads, d, d ** -0.5)
 
     def _gn(self, r, x, x2, c0, c1, hw, groups, eps, gamma, beta, silu, out):
         # (round 1-2 could also take the statistics from the producing conv's epilogue (chanstat_out): slower than the separate,
@@ -1073,7 +1174,7 @@ class Engine:
 
     def prepare(self, H: int, W: int, steps: int, strength: float, controlnet_scale: float = 1.0,
                 use_controlnet: bool = True, use_graph: Optional[bool] = None, autotune: bool = True, batch: int = 1,
-                ref_mode: bool = False, device_seed: bool = False):
+                ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False):
         """Fix the frame geometry and schedule; build the static program and capture it into a hipGraph
         (the reference's intent at videopipeline.py:35-47, `compile_model`).
 
@@ -1090,7 +1191,14 @@ class Engine:
         launch (include/vsd.h THE NOISE CONTRACT; `submit_*(seeds=...)`): the program records vsd_add_noise_seeded /
         vsd_lcm_step_seeded in place of the `_dev` forms -- launch for launch -- and reads the seeds from `seed_dev`, a buffer of
         this engine's own; there is no host noise table.  A new seed is 8 bytes per frame copied ahead of the launch: no drain,
-        no `update_options`, no re-capture.  Default: the CPU-contract draws of `host_noise`, the same for every frame."""
+        no `update_options`, no re-capture.  Default: the CPU-contract draws of `host_noise`, the same for every frame.
+
+        frame_prompts: every frame of the launch has a prompt of its own (`use_prompts`): the program reads K / V^T from a per-frame block
+        (FramePromptLayout) and records every cross-attention in the explicit form -- q GEMM over all B*hw rows, attention with image b on
+        its own key rows / V^T columns, out GEMM -- at all widths (no absorbed weights: they would be per frame).  A cached prompt enters
+        a frame slot by one `prompt_install` launch ahead of the program.  Default: one prompt per launch, as before."""
+        if frame_prompts and not hasattr(self.ops, "prompt_install"):
+            raise ValueError("frame_prompts=True needs the op prompt_install, which this ops object does not have")
         if device_seed and not all(hasattr(self.ops, f) for f in ("add_noise_seeded", "lcm_step_seeded")):
             raise ValueError("device_seed=True needs the ops add_noise_seeded and lcm_step_seeded, which this ops object does not have")
         if batch < 1:
@@ -1107,11 +1215,21 @@ class Engine:
         if H % 8 or W % 8:
             raise ValueError("height and width must be multiples of 8 (TAESD / latent stride)")
         src = self._want if self._want is not None else self.family.get("prompt")
-        if src is None:
+        if src is None and not (frame_prompts and getattr(self, "_want_list", None)):
             raise RuntimeError("set_text_embeds must be called before prepare")
-        if self.pblock is None or self.pblock.layout is not src.layout:
+        if frame_prompts:
+            tl = self._frame_sources(batch)[0].layout.tl
+            lays = self.family.setdefault("frame_layouts", {})  # (one layout OBJECT per (text length, frames), as for `layouts`)
+            lay = lays.get((tl, batch))
+            if lay is None:
+                lay = lays[(tl, batch)] = FramePromptLayout(self._nets(), tl, batch)
+            if self.pblock is None or self.pblock.layout is not lay:
+                self.pblock = PromptBlock(self.ops, lay)
+                self._slot_src = [None] * batch
+        elif self.pblock is None or self.pblock.layout is not src.layout:
             self.pblock = PromptBlock(self.ops, src.layout)
             self._installed = None
+        self.frame_prompts = bool(frame_prompts)
         if use_controlnet and self.cn is None:
             raise RuntimeError("no ControlNet weights loaded")
         if ref_mode and (batch != 1 or use_controlnet or (H // 8) * (W // 8) % 8):
@@ -1277,7 +1395,7 @@ class Engine:
         self.program = r.flavor(0 if self.overlap_controlnet or not self._twin_now else 1)
         self.program_serial = r.flavor(1) if self._twin_now and self.overlap_controlnet and use_controlnet else self.program
         self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=n, batch=B,
-                         ref_mode=bool(ref_mode), device_seed=bool(device_seed), tuned_for_lanes=bool(self.tune_for_lanes),
+                         ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), tuned_for_lanes=bool(self.tune_for_lanes),
                          sizes=sizes, timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=a.peak)
         # per-shape kernel configuration (timed once per shape, cached in ops.tile_override), warm-up, capture
         torch.cuda.synchronize() if torch.cuda.is_available() else None  # allocation fills vs. kernel streams

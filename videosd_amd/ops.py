@@ -1009,6 +1009,13 @@ class HipOps:
         self.ctx.call("vsd_lcm_step_seeded", self._p(eps), self._p(sample), self._p(seeds_dev), int(kind), int(draw), self._p(coef_dev),
                       hw, batch, self._p(prev), self._p(denoised), self._p(dec_in), self.s)
 
+    def prompt_install(self, src_buf, dst_buf, segs_dev, nseg: int, frame: int):
+        """one cached prompt (PromptBlock.buf of a PromptLayout) into frame slot `frame` of a per-frame block (FramePromptLayout), one launch on
+        this object's own stream (include/vsd.h vsd_prompt_install; csrc/prompt_install.hip).  segs_dev: int64 [nseg][6] in device memory
+        (engine.prompt_segments).  The library checks a table when it first sees it and remembers it by address: the table is kept alive here."""
+        self.__dict__.setdefault("_seg_tables", {})[segs_dev.data_ptr()] = segs_dev
+        self.ctx.call("vsd_prompt_install", self._p(src_buf), self._p(dst_buf), self._p(segs_dev), int(nseg), int(frame), self.raw_stream(0))
+
     def adain(self, x, stats, stats_ref, rows, c, out, eps=1e-6):
         """reference-only AdaIN: per-channel re-normalisation of x to the banked statistics (fp32 [c][2] sum / sumsq)"""
         self.ctx.call("vsd_adain", self._p(x), self._p(stats), self._p(stats_ref), rows, c, eps, self._p(out), self.s)

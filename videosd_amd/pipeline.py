@@ -52,6 +52,7 @@ def load_or_synthesize(spec, prefix: str, filename: str, device, snapshot_file: 
         return w, path
     return W.synthesize(spec, prefix, device=device), "synthetic"
 
+_FRAME_PROMPTS = ("frame_prompts", True)  # ... and in THAT mode (after _DEVICE_SEED when both are on)
 _DEVICE_SEED = ("device_seed", True)  # the element a plan key ends with in that mode (no prompt key of an SDXL plan looks like it)
 
 
@@ -78,6 +79,13 @@ class VideoSDPipeline:
         self.device_seed = bool(kwargs.get("device_seed", False))
         if self.device_seed:
             self.per_frame_seed = True
+        # extension, off by default: every frame of a launch has a prompt of its own -- `infer_batch` / `submit_batch` take `prompts`, one per
+        # frame, and a worker coalesces frames of sessions that differ in `prompt` (`per_frame_prompt`, read by dispatch.py).  The program
+        # then reads K / V^T per frame and runs every cross-attention in the explicit form (Engine.prepare(frame_prompts=True)).  Off:
+        # one prompt per launch, the absorbed form at the wide levels.
+        self.frame_prompts = bool(kwargs.get("frame_prompts", False))
+        if self.frame_prompts:
+            self.per_frame_prompt = True
         # launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on
         # launch stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch
         self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
@@ -260,7 +268,12 @@ class VideoSDPipeline:
         the prompt cache; nothing in flight is disturbed."""
         return self._cache_prompt(key, embeds)
 
-    def _cache_prompt(self, key, embeds=None, prompt=None):
+    def _prompts_in_use(self):
+        """ids of the cache entries a submitted, not yet collected launch of a `frame_prompts` engine reads from (its installs may not have
+        executed yet) -- the LRU never drops those"""
+        return {id(b) for e in self._outstanding for b in getattr(e, "_slot_src", ()) if b is not None}
+
+    def _cache_prompt(self, key, embeds=None, prompt=None, keep=()):
         blk = self._prompts.get(key)
         if blk is not None and embeds is not None and blk.text is not None:
             # the same embeddings for a key this worker already holds (a repeated sync, a dispatcher that lost track of what the
@@ -274,7 +287,14 @@ class VideoSDPipeline:
             blk = self.model.build_prompt(embeds if embeds is not None else self.encode_prompt(prompt))
             self._prompts[key] = blk
             self._note("prompt", t0)
-            while len(self._prompts) > max(1, self.max_prompts):  # least recently used first; an engine that still holds an
+            if getattr(self, "frame_prompts", False):
+                # (a launch names several entries: never one of the launch being put together (`keep`), never one in use -- the cache then grows)
+                busy = self._prompts_in_use()
+                for k in [k for k, b in self._prompts.items() if k != key and k not in keep and id(b) not in busy]:
+                    if len(self._prompts) <= max(1, self.max_prompts):
+                        break
+                    del self._prompts[k]
+            while not getattr(self, "frame_prompts", False) and len(self._prompts) > max(1, self.max_prompts):  # least recently used first; an engine that still holds an
                 self._prompts.popitem(last=False)                 # evicted block keeps it alive until it switches
         self._prompts.move_to_end(key)
         return blk
@@ -356,15 +376,18 @@ class VideoSDPipeline:
                                 controlnet=controlnet, seed=seed, controlnet_scale=controlnet_scale)[0]
 
     def infer_batch(self, imgs, prompt=["pixar, cg"], height=360, width=640, strength=0.4, steps=20, guidance_scale=7.5,
-                    ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1):
+                    ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1, prompts=None):
         """Several frames (of different sessions, or consecutive frames of one stream) with the SAME options through
         one batched launch: the result `infer` gives each frame, up to kernel rounding (frames are denoised independently), one pass over the
         weights for all of them.  Extension of the reference surface; `RemotePipeline(batch=B)` coalesces queued
-        `infer` calls into this."""
+        `infer` calls into this.
+        prompts (objects built with `frame_prompts=True`): one prompt per frame, each what `prompt` accepts; frame i is then what `infer`
+        gives it with prompts[i].  None: `prompt` for every frame."""
+        extra = {} if prompts is None else {"prompts": prompts}
         return self.collect_batch(self.submit_batch(imgs, prompt=prompt, height=height, width=width, strength=strength,
                                                     steps=steps, guidance_scale=guidance_scale, ref=ref,
                                                     style_fidelity=style_fidelity, controlnet=controlnet, seed=seed,
-                                                    controlnet_scale=controlnet_scale))
+                                                    controlnet_scale=controlnet_scale, **extra))
 
     def warm_up(self, batches=(1,), lanes: int = 1, **options):
         """Prepare every (batch size, lane) engine a stream with these `infer` options will use -- plan, captured graph
@@ -382,12 +405,28 @@ class VideoSDPipeline:
         return ready
 
     def submit_batch(self, imgs, lane: int = 0, prompt=["pixar, cg"], height=360, width=640, strength=0.4, steps=20,
-                     guidance_scale=7.5, ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1):
+                     guidance_scale=7.5, ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1, prompts=None):
         """First half of `infer_batch`: crop / resize, upload, enqueue -- returns a handle for `collect_batch` without
         waiting for the GPU.  `lane` picks one of the prepared engines of that (options, batch size): two lanes keep two
         launches in flight while the host works on the frames around them (the worker loop of dispatch.py does that)."""
         if not 0 <= int(lane) < self.max_lanes:
             raise ValueError(f"lane {lane}: this pipeline was built for {self.max_lanes} launch lane(s) (kwarg `lanes`)")
+        plist = None
+        if prompts is not None:
+            if not getattr(self, "frame_prompts", False):
+                raise ValueError("prompts= (one prompt per frame) needs a pipeline built with frame_prompts=True; this one runs one prompt per launch (`prompt`)")
+            plist = list(prompts)
+            if len(plist) != len(imgs):
+                raise ValueError(f"prompts must hold one prompt per frame: {len(plist)} prompt(s) for {len(imgs)} frame(s)")
+        elif getattr(self, "frame_prompts", False):
+            plist = [prompt] * len(imgs)
+        if plist is not None:
+            pkeys = [p if isinstance(p, str) else tuple(p) for p in plist]
+            if len(set(pkeys)) > 1 and (self.is_xl or (bool(ref) and self.honor_ref_flag)):
+                raise ValueError("prompts: more than one distinct prompt in a launch is not possible here: " +
+                                 ("an SDXL program has the pooled text embedding of ITS prompt baked in" if self.is_xl else
+                                  "reference-only frames run one frame per launch"))
+            prompt = plist[0]
         t0 = time.perf_counter()
         # WebRTC frames (planar YUV 4:2:0: an `I420Frame`, or an av.VideoFrame by duck typing): when EVERY frame of the launch is one,
         # the planes go to the device as they are and the result comes back as I420 (`_i420_on_device`); otherwise such a frame is
@@ -414,7 +453,10 @@ class VideoSDPipeline:
             imgs = [im.resize((width, height), resample=Image.Resampling.LANCZOS) for im in imgs]
         self._note("crop_resize", t0)
         pkey = prompt if isinstance(prompt, str) else tuple(prompt)
-        pblock = self._cache_prompt(pkey, prompt=prompt)  # cached: nothing to do; new: ~1 ms on the GPU, nobody waits
+        if plist is not None:  # one cache entry per frame (the same object for equal prompts)
+            pblock = [self._cache_prompt(k, prompt=p, keep=pkeys) for k, p in zip(pkeys, plist)]
+        else:
+            pblock = self._cache_prompt(pkey, prompt=prompt)  # cached: nothing to do; new: ~1 ms on the GPU, nobody waits
         use_cn = False if self.is_xl else (bool(controlnet) if self.honor_controlnet_flag else True)
         use_ref = bool(ref) and self.honor_ref_flag and not self.is_xl
         if use_ref:
@@ -431,7 +473,7 @@ class VideoSDPipeline:
 
         n_eff = len(lcm_timesteps(float(strength), int(steps)))  # ValueError for an empty schedule: the caller's problem
         # (SDXL: the pooled text embedding is baked into the time embeddings at `prepare`, so the prompt is part of the program)
-        plan_key = (height, width, int(steps), n_eff, use_cn, use_ref) + ((pkey,) if self.is_xl else ()) + ((_DEVICE_SEED,) if getattr(self, "device_seed", False) else ())
+        plan_key = (height, width, int(steps), n_eff, use_cn, use_ref) + ((pkey,) if self.is_xl else ()) + ((_DEVICE_SEED,) if getattr(self, "device_seed", False) else ()) + ((_FRAME_PROMPTS,) if plist is not None else ())
         seeds = None
         if getattr(self, "device_seed", False):
             seeds = [seed] * len(imgs) if isinstance(seed, (int, np.integer)) else list(seed)
@@ -440,7 +482,8 @@ class VideoSDPipeline:
             seeds = [int(v) for v in seeds]
         opts = (float(strength), float(controlnet_scale))
         eng = self._engine_for(plan_key, opts, len(imgs), lane, prompt=pblock, prompt_text=prompt)
-        eng.use_prompt(pblock)  # this lane's launch reads ITS copy of the constants: the other lanes may run other prompts
+        # this lane's launch reads ITS copy of the constants: the other lanes may run other prompts
+        eng.use_prompts(pblock) if plist is not None else eng.use_prompt(pblock)
         if use_ref and getattr(eng, "_ref_epoch", None) != self._ref_epoch:
             rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), width, height), dtype=np.uint8)
             eng.ops.upload(eng.ref_u8, torch.from_numpy(np.array(rf, copy=True)))  # (PIL's buffer is read-only)
@@ -462,6 +505,8 @@ class VideoSDPipeline:
         self._outstanding.append(eng)
         self._lanes_busy.append(int(lane))
         self._note("upload_enqueue", t0)
+        if plist is not None:  # (the handle keeps the launch's cache entries alive: their installs may not have executed yet)
+            return (eng, len(imgs), yuv if any(yuv) else None, i420 is not None, tuple(pblock))
         if any(yuv):  # (which results go back as I420, and whether the device converts them)
             return (eng, len(imgs), yuv, i420 is not None)
         return (eng, len(imgs))
@@ -562,6 +607,8 @@ class VideoSDPipeline:
                 pk += (o["prompt"] if isinstance(o["prompt"], str) else tuple(o["prompt"]),)
             if getattr(self, "device_seed", False):
                 pk += (_DEVICE_SEED,)
+            if getattr(self, "frame_prompts", False):
+                pk += (_FRAME_PROMPTS,)
             plan = self._plans.get(pk)
             if plan is None:
                 return False
@@ -607,7 +654,7 @@ class VideoSDPipeline:
         else:
             eng = plan["root"].make_slot(lane=lane)
         if prompt is not None:
-            eng.use_prompt(prompt)
+            eng.use_prompts(prompt) if isinstance(prompt, list) else eng.use_prompt(prompt)
         if self.is_xl:  # micro-conditioning: original size = target size = the frame size, no crop
             eng.set_added_cond(self.encode_pooled(prompt_text if prompt_text is not None else ""), (height, width, 0, 0, height, width))
         # (every engine is captured both ways -- ControlNet encoder on the lane's side stream / everything on the lane's own
@@ -617,6 +664,8 @@ class VideoSDPipeline:
         # fastest alone.  Fixed per plan, the same on every lane (same bits whichever lane a frame lands on).
         eng.tune_for_lanes = self.max_lanes >= 3 and batch > 1
         mode = {"device_seed": True} if _DEVICE_SEED in plan_key[6:] else {}
+        if _FRAME_PROMPTS in plan_key[6:]:
+            mode["frame_prompts"] = True
         eng.prepare(height, width, steps, strength, controlnet_scale=cn_scale, use_controlnet=use_cn, batch=batch, ref_mode=use_ref,
                     autotune=self.tuning_mode != "table", **mode)
         eng._ref_epoch = None
@@ -677,6 +726,9 @@ class VideoSDPipeline:
         `frames_per_launch` > 1: the coalesced program of `infer_batch`.  Returns the exporter's summary (videosd_amd/plan.py)."""
         from .plan import export_plan
 
+        if getattr(self, "frame_prompts", False):
+            raise ValueError("export_plan: this pipeline was built with frame_prompts=True; a plan file holds ONE prompt's constants and the C "
+                             "library has no per-frame prompt entry point yet: export from a pipeline built without it")
         self._require_idle("export a plan")
         w, h = int(options.get("width", 640)), int(options.get("height", 360))
         imgs = [Image.new("RGB", (w, h), (127, 127, 127)) for _ in range(int(frames_per_launch))]

@@ -227,6 +227,9 @@ def export_plan(engine, path: str) -> dict:
     ops = engine.ops
     if engine.plan is None:
         raise RuntimeError("export_plan: prepare the engine first")
+    if engine.plan.get("frame_prompts"):
+        raise ValueError("export_plan: this engine was prepared with frame_prompts=True; a plan file holds ONE prompt's constants (per-frame "
+                         "prompts have no C entry point yet): export the plan of an engine prepared without it")
     ops.synchronize()
     calls = []
 
