@@ -250,7 +250,7 @@ int vsd_add_noise_dev(vsd_ctx* ctx, const void* x0, const void* noise_f32, const
 int vsd_lcm_step_dev(vsd_ctx* ctx, const void* eps, const void* sample, const void* noise_f32, const void* coef_dev, int hw,
                      int batch, void* prev, void* denoised, void* dec_in, void* stream);
 
-/* ---- seeded noise on the device (csrc/noise.hip) ------------------------------------------------------------------------------------
+/* ---- seeded noise on the device; the scheduler arithmetic (csrc/noise.hip) ----------------------------------------------------------
  * The reference's frame loop sends `seed` with every frame (server.py:181-182) and on its CUDA deployment the seed reaches the initial
  * noise.  The default here keeps the CPU-contract draws of Engine.host_noise (one table per plan, the same for every frame); with these
  * entry points the noise is instead a pure function of (seed, kind, draw, pixel, channel), evaluated inside the captured program.
@@ -268,10 +268,21 @@ int vsd_lcm_step_dev(vsd_ctx* ctx, const void* eps, const void* sample, const vo
  *   This is NOT torch's CUDA stream for the same seed (that mapping depends on the device's grid size).
  * vsd_noise_fill: one draw of hw pixels; raw = 0: fp32 [4][hw], the layout vsd_add_noise_dev / vsd_lcm_step_dev read (out 4-byte
  *   aligned); raw = 1: the integers X as u32 [hw][4] (out 16-byte aligned).
- * vsd_add_noise_seeded / vsd_lcm_step_seeded: vsd_add_noise_dev / vsd_lcm_step_dev -- the same arithmetic, operation for operation, the
- *   same bits as vsd_noise_fill followed by them -- with the noise pointer replaced by (seeds_dev: u32 [batch][2] = (low, high) per
- *   image in DEVICE memory, kind, draw): image b of the launch uses seeds_dev[b].  vsd_lcm_step_seeded: draw <= 0 = this step adds no
- *   noise (vsd_lcm_step_dev with noise_f32 NULL; seeds_dev may then be NULL). */
+ * vsd_add_noise_seeded / vsd_lcm_step_seeded: vsd_add_noise_dev / vsd_lcm_step_dev -- the same kernel source, instantiated with another
+ *   noise source, so the same bits as vsd_noise_fill followed by them -- with the noise pointer replaced by (seeds_dev: u32 [batch][2] =
+ *   (low, high) per image in DEVICE memory, kind, draw): image b of the launch uses seeds_dev[b].  vsd_lcm_step_seeded: draw <= 0 = this
+ *   step adds no noise (vsd_lcm_step_dev with noise_f32 NULL; seeds_dev may then be NULL).
+ * THE SCHEDULER ARITHMETIC (fixed; tests/golden/scheduler_bits.json pins its bits).  One body in csrc/noise.hip, compiled with fp
+ *   contraction off, serves vsd_add_noise, vsd_lcm_step and their _dev and _seeded forms.  Per pixel and channel 0..3, in fp32: x, e
+ *   and xs are the fp16 inputs converted exactly, n is the pixel's normal of that channel, an fma rounds once and every other
+ *   operation rounds by itself.
+ *   - add_noise:  out = fp16(fma(sqrt_a, x, sqrt_b * n)).
+ *   - lcm_step:   px0 = fma(-sqrt_b, e, xs) / sqrt_a;   d = fma(c_skip, xs, c_out * px0), an fp32 value.
+ *                 denoised = fp16(d): rounded from the fp32 d, not from the unrounded fma.
+ *                 prev = fp16(sqrt_a_prev * d + sqrt_b_prev * n): a multiply, a multiply and an add, on the fp32 d, not on fp16(d).
+ *                 Without noise prev = denoised.
+ *                 dec_in = fp16(tanhf(fp32(denoised) / 3) * 3).
+ *   - channels 4..7 of every output are written as zero. */
 int vsd_noise_fill(vsd_ctx* ctx, uint32_t seed_lo, uint32_t seed_hi, int kind, int draw, int hw, int raw, void* out, void* stream);
 int vsd_add_noise_seeded(vsd_ctx* ctx, const void* x0, const void* seeds_dev, int kind, int draw, const void* coef_dev, int hw, int batch,
                          void* out, void* stream);

@@ -108,7 +108,7 @@ def test_the_normals_are_within_the_fp32_bound_of_the_fp64_restatement(ops):
 
 
 # ------------------------------------------------------------------------------------------ 3. fused = fill + the existing kernel
-@pytest.mark.parametrize("hw", [15, 4097])
+@pytest.mark.parametrize("hw", [15, 4097, 262145])
 def test_the_seeded_scheduler_kernels_equal_fill_plus_the_existing_kernels_bit_for_bit(ops, hw):
     B, seeds = 3, (7, 8, 7)
     g = torch.Generator().manual_seed(hw)

@@ -1,18 +1,18 @@
-// Seeded noise on the device (include/vsd.h, THE NOISE CONTRACT): the normal draws of a frame as a pure function of
-// (seed, kind, draw, pixel, channel) -- Philox4x32-10, one block per latent pixel = its four channels, Box-Muller in fp32 -- evaluated
-// in the thread that uses them.  vsd_noise_fill writes a draw out (the layout vsd_add_noise_dev / vsd_lcm_step_dev read, or the raw
-// integers); vsd_add_noise_seeded / vsd_lcm_step_seeded are those two kernels with the noise pointer replaced by per-image seeds in
-// device memory: a captured graph then follows a new seed per frame with an 8-byte copy per image, nothing re-captured.
-// Launch-bound like the rest of the scheduler arithmetic (at most batch * hw = 5 * 4096 threads at 512 x 512): 10 fixed rounds of two
-// 32 x 32 -> 64 multiplies (a v_mul_lo_u32 / v_mul_hi_u32 pair each, quarter rate), no data-dependent trip count, one thread per pixel.
+// The scheduler arithmetic and the seeded noise that can feed it (include/vsd.h: THE SCHEDULER ARITHMETIC, THE NOISE CONTRACT).
+// One add_noise body and one lcm_step body serve all six entry points: vsd_add_noise / vsd_lcm_step (coefficients by value, one image),
+// the _dev forms (coefficients in device memory, a batch per launch: a captured graph follows a new strength by rewriting the floats)
+// and the _seeded forms (the noise table replaced by per-image seeds in device memory: a captured graph follows a new seed per frame
+// with an 8-byte copy per image, nothing re-captured).  The normal draws of a frame are a pure function of (seed, kind, draw, pixel,
+// channel) -- Philox4x32-10, one block per latent pixel = its four channels, Box-Muller in fp32 -- evaluated in the thread that uses
+// them; vsd_noise_fill writes a draw out (the table layout, or the raw integers).
+// Launch-bound (at most batch * hw = 5 * 4096 threads at 512 x 512): 10 fixed rounds of two 32 x 32 -> 64 multiplies (a v_mul_lo_u32 /
+// v_mul_hi_u32 pair each, quarter rate), no data-dependent trip count, one thread per pixel.
 #include <stdarg.h>
 
 #include "common.h"
 
-// The seeded scheduler kernels must give the bits of add_noise_dev_kernel / lcm_step_dev_kernel (csrc/elementwise.hip), whose source
-// leaves the choice of what becomes an fma to the compiler (fp-contract "fast" is hipcc's default), and that choice follows the code
-// around an expression: a kernel with the same source text but no noise branch got mul, mul, add where the _dev kernel has mul, fma.
-// So nothing in this file is contracted, and the fused operations of the _dev kernels' gfx950 code are written out where they occur.
+// The bits of every frame are these kernels' fp32 operations, so the source states each one: nothing in this file is contracted by the
+// compiler, and an fma is written where the contract has one.
 #pragma clang fp contract(off)
 
 namespace {
@@ -72,18 +72,36 @@ __global__ void noise_fill_kernel(uint32_t seed_lo, uint32_t seed_hi, uint32_t k
   }
 }
 
-struct StepCoef {
-  float sa, sb, cskip, cout, sap, sbp;
+// Where a pixel's four normals come from: the fp32 [4][hw] table every image of the launch shares, or the image's seed.
+struct TableNoise {
+  const float* __restrict__ table;
+  __device__ Normal4 operator()(int hw, uint32_t, uint32_t i) const {
+    return Normal4{{table[i], table[(size_t)hw + i], table[(size_t)2 * hw + i], table[(size_t)3 * hw + i]}};
+  }
 };
 
-// add_noise_dev_kernel (csrc/elementwise.hip), operation for operation as compiled (sa * x + sb * n is fma(sa, x, sb * n) there), with
-// the draw computed here; blockIdx.y = image of the launch
-__global__ void add_noise_seeded_kernel(const half_t* __restrict__ x0, const uint32_t* __restrict__ seeds, uint32_t kind, uint32_t draw,
-                                        const float* __restrict__ coef, int hw, half_t* __restrict__ out) {
+struct SeededNoise {
+  const uint32_t* __restrict__ seeds;  // [batch][2] = (low, high)
+  uint32_t kind, draw;
+  __device__ Normal4 operator()(int, uint32_t image, uint32_t i) const { return seeded_normals(seeds[2 * image], seeds[2 * image + 1], kind, draw, i); }
+};
+
+// Where the coefficients {sa, sb, cskip, cout, sap, sbp} come from: the first N of them by value (add_noise takes two, a step six), or
+// floats in device memory (`const float*`; add_noise reads the first two alone).
+template <int N>
+struct CoefValues {
+  float v[N];
+  __device__ float operator[](int j) const { return v[j]; }
+};
+
+// THE SCHEDULER ARITHMETIC, per channel 0..3 in fp32 (channels 4..7 are written as zero); blockIdx.y = image of the launch:
+//   out = fp16(fma(sa, x, sb * n))
+template <class Noise, class Coef>
+__global__ void add_noise_kernel(const half_t* __restrict__ x0, Noise noise, Coef k, int hw, half_t* __restrict__ out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= hw) return;
-  const float sa = coef[0], sb = coef[1];
-  const Normal4 nz = seeded_normals(seeds[2 * blockIdx.y], seeds[2 * blockIdx.y + 1], kind, draw, (uint32_t)i);
+  const float sa = k[0], sb = k[1];
+  const Normal4 nz = noise(hw, blockIdx.y, (uint32_t)i);
   const size_t row = (size_t)blockIdx.y * hw + i;
   half8 x = *reinterpret_cast<const half8*>(x0 + row * 8);
   half8 o = (half8){0, 0, 0, 0, 0, 0, 0, 0};
@@ -92,17 +110,16 @@ __global__ void add_noise_seeded_kernel(const half_t* __restrict__ x0, const uin
   *reinterpret_cast<half8*>(out + row * 8) = o;
 }
 
-// lcm_step_dev_kernel (csrc/elementwise.hip), operation for operation as compiled: xs - sb * e and cout * px0 + cskip * xs are one fma
-// each, sap * d + sbp * n is not.  NOISE = false: the step that adds none (its noise pointer NULL)
-template <bool NOISE>
-__global__ void lcm_step_seeded_kernel(const half_t* __restrict__ eps, const half_t* __restrict__ sample, const uint32_t* __restrict__ seeds,
-                                       uint32_t kind, uint32_t draw, const float* __restrict__ coef, int hw, half_t* __restrict__ prev,
-                                       half_t* __restrict__ den, half_t* __restrict__ dec_in) {
+//   px0 = fma(-sb, e, xs) / sa;  d = fma(cskip, xs, cout * px0);  den = fp16(d);
+//   prev = fp16(sap * d + sbp * n) as mul, mul, add (NOISE = false, the step that adds none: prev = den);  dec_in = fp16(tanhf(den / 3) * 3)
+template <bool NOISE, class Noise, class Coef>
+__global__ void lcm_step_kernel(const half_t* __restrict__ eps, const half_t* __restrict__ sample, Noise noise, Coef k, int hw,
+                                half_t* __restrict__ prev, half_t* __restrict__ den, half_t* __restrict__ dec_in) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= hw) return;
-  const StepCoef k = {coef[0], coef[1], coef[2], coef[3], coef[4], coef[5]};
+  const float sa = k[0], sb = k[1], cskip = k[2], cout = k[3], sap = k[4], sbp = k[5];
   Normal4 nz = {{0.f, 0.f, 0.f, 0.f}};
-  if (NOISE) nz = seeded_normals(seeds[2 * blockIdx.y], seeds[2 * blockIdx.y + 1], kind, draw, (uint32_t)i);
+  if (NOISE) nz = noise(hw, blockIdx.y, (uint32_t)i);
   const size_t row = (size_t)blockIdx.y * hw + i;
   half8 e = *reinterpret_cast<const half8*>(eps + row * 8);
   half8 x = *reinterpret_cast<const half8*>(sample + row * 8);
@@ -110,17 +127,30 @@ __global__ void lcm_step_seeded_kernel(const half_t* __restrict__ eps, const hal
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     float xs = (float)x[c];
-    float px0 = __builtin_fmaf(-k.sb, (float)e[c], xs) / k.sa;
-    float d = __builtin_fmaf(k.cskip, xs, k.cout * px0);
-    asm volatile("" : "+v"(d));  // d exists in fp32 before it is rounded to fp16, as there: no v_fma_mixlo_f16 (emits nothing)
+    float px0 = __builtin_fmaf(-sb, (float)e[c], xs) / sa;
+    float d = __builtin_fmaf(cskip, xs, cout * px0);
+    asm volatile("" : "+v"(d));  // d exists in fp32 before it is rounded to fp16: no v_fma_mixlo_f16 (emits nothing)
     od[c] = (half_t)d;
-    float pv = NOISE ? k.sap * d + k.sbp * nz.z[c] : d;  // (mul, mul, add there too)
+    float pv = NOISE ? sap * d + sbp * nz.z[c] : d;
     op[c] = (half_t)pv;
     oi[c] = (half_t)(tanhf((float)od[c] / 3.0f) * 3.0f);
   }
   if (prev) *reinterpret_cast<half8*>(prev + row * 8) = op;
   if (den) *reinterpret_cast<half8*>(den + row * 8) = od;
   if (dec_in) *reinterpret_cast<half8*>(dec_in + row * 8) = oi;
+}
+
+template <class Noise, class Coef>
+void launch_add_noise(hipStream_t s, const void* x0, Noise noise, Coef k, int hw, int batch, void* out) {
+  hipLaunchKernelGGL((add_noise_kernel<Noise, Coef>), dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)x0, noise, k, hw, (half_t*)out);
+}
+
+template <class Noise, class Coef>
+void launch_lcm_step(hipStream_t s, const void* eps, const void* sample, bool noisy, Noise noise, Coef k, int hw, int batch, void* prev,
+                     void* den, void* dec_in) {
+  auto kernel = noisy ? lcm_step_kernel<true, Noise, Coef> : lcm_step_kernel<false, Noise, Coef>;
+  hipLaunchKernelGGL(kernel, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)eps, (const half_t*)sample, noise, k, hw, (half_t*)prev,
+                     (half_t*)den, (half_t*)dec_in);
 }
 
 }  // namespace
@@ -135,6 +165,50 @@ extern "C" int vsd_noise_fill(vsd_ctx* ctx, uint32_t seed_lo, uint32_t seed_hi, 
   return ls.finish();
 }
 
+extern "C" int vsd_add_noise(vsd_ctx* ctx, const void* x0, const void* noise_f32, float sqrt_a, float sqrt_b, int hw,
+                             void* out, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!x0 || !noise_f32 || !out || hw <= 0) return vsd_fail(ctx, VSD_ERR_ARG, "add_noise: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  launch_add_noise(s, x0, TableNoise{(const float*)noise_f32}, CoefValues<2>{{sqrt_a, sqrt_b}}, hw, 1, out);
+  return ls.finish();
+}
+
+extern "C" int vsd_lcm_step(vsd_ctx* ctx, const void* eps, const void* sample, const void* noise_f32,
+                            const float* coef_host, int hw, void* prev, void* denoised, void* dec_in, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!eps || !sample || !coef_host || hw <= 0) return vsd_fail(ctx, VSD_ERR_ARG, "lcm_step: bad arguments");
+  CoefValues<6> k = {{coef_host[0], coef_host[1], coef_host[2], coef_host[3], coef_host[4], coef_host[5]}};
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  launch_lcm_step(s, eps, sample, noise_f32 != nullptr, TableNoise{(const float*)noise_f32}, k, hw, 1, prev, denoised, dec_in);
+  return ls.finish();
+}
+
+extern "C" int vsd_add_noise_dev(vsd_ctx* ctx, const void* x0, const void* noise_f32, const void* coef_dev, int hw, int batch,
+                                 void* out, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!x0 || !noise_f32 || !coef_dev || !out || hw <= 0 || batch < 1 || batch > 65535)
+    return vsd_fail(ctx, VSD_ERR_ARG, "add_noise_dev: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  launch_add_noise(s, x0, TableNoise{(const float*)noise_f32}, (const float*)coef_dev, hw, batch, out);
+  return ls.finish();
+}
+
+extern "C" int vsd_lcm_step_dev(vsd_ctx* ctx, const void* eps, const void* sample, const void* noise_f32, const void* coef_dev,
+                                int hw, int batch, void* prev, void* denoised, void* dec_in, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!eps || !sample || !coef_dev || hw <= 0 || batch < 1 || batch > 65535)
+    return vsd_fail(ctx, VSD_ERR_ARG, "lcm_step_dev: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  launch_lcm_step(s, eps, sample, noise_f32 != nullptr, TableNoise{(const float*)noise_f32}, (const float*)coef_dev, hw, batch, prev, denoised,
+                  dec_in);
+  return ls.finish();
+}
+
 extern "C" int vsd_add_noise_seeded(vsd_ctx* ctx, const void* x0, const void* seeds_dev, int kind, int draw, const void* coef_dev, int hw, int batch,
                                     void* out, void* stream) {
   if (!ctx) return VSD_ERR_ARG;
@@ -142,8 +216,7 @@ extern "C" int vsd_add_noise_seeded(vsd_ctx* ctx, const void* x0, const void* se
     return vsd_fail(ctx, VSD_ERR_ARG, "add_noise_seeded: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
-  hipLaunchKernelGGL(add_noise_seeded_kernel, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)x0, (const uint32_t*)seeds_dev,
-                     (uint32_t)kind, (uint32_t)draw, (const float*)coef_dev, hw, (half_t*)out);
+  launch_add_noise(s, x0, SeededNoise{(const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw}, (const float*)coef_dev, hw, batch, out);
   return ls.finish();
 }
 
@@ -154,12 +227,7 @@ extern "C" int vsd_lcm_step_seeded(vsd_ctx* ctx, const void* eps, const void* sa
     return vsd_fail(ctx, VSD_ERR_ARG, "lcm_step_seeded: bad arguments");
   hipStream_t s = (hipStream_t)stream;
   LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
-  if (draw > 0)
-    hipLaunchKernelGGL(lcm_step_seeded_kernel<true>, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)eps, (const half_t*)sample,
-                       (const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw, (const float*)coef_dev, hw, (half_t*)prev, (half_t*)denoised,
-                       (half_t*)dec_in);
-  else
-    hipLaunchKernelGGL(lcm_step_seeded_kernel<false>, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)eps, (const half_t*)sample,
-                       (const uint32_t*)seeds_dev, 0u, 0u, (const float*)coef_dev, hw, (half_t*)prev, (half_t*)denoised, (half_t*)dec_in);
+  launch_lcm_step(s, eps, sample, draw > 0, SeededNoise{(const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw}, (const float*)coef_dev, hw, batch,
+                  prev, denoised, dec_in);
   return ls.finish();
 }

@@ -1278,16 +1278,31 @@ class Engine:
         self._cn_scale_consts = c[2 + 6 * n:]
         # noise draws: the reference resets the global CPU generator to a fresh-Generator state on every
         # frame (videopipeline.py:126), so for a fixed shape the draws are the same every frame.
-        draws = ref_draws = None
+        # Where the noise comes from is chosen here, once: add_noise(r, x0, kind, draw, coef, batch, out) and lcm_step(r, eps, cur, draw,
+        # coef, batch, nxt, den, dec_in) record the scheduler ops of either source (include/vsd.h: kind 0 draw d = noise[d], kind 1 draw
+        # d = noise_ref[d]; a step with draw 0 adds none).
+        ref_draws = None
         if device_seed:
             # one seed per frame of the launch, u32 (low, high) pairs = little-endian u64: this engine's own (a slot has its own)
             self.noise = self.noise_ref = None
             self.seed_dev = seeds = ops.zeros(B, dtype=torch.int64)
             self._seed_host = torch.zeros(B, dtype=torch.int64, pin_memory=torch.cuda.is_available())
+
+            def add_noise(r, x0, kind, draw, coef, batch, out):
+                r.add_noise_seeded(x0, seeds, kind, draw, coef, hw0, batch, out)
+
+            def lcm_step(r, eps, cur, draw, coef, batch, nxt, den, dec_in):
+                r.lcm_step_seeded(eps, cur, seeds, 0, draw, coef, hw0, batch, nxt, den, dec_in)
         else:
             self.seed_dev = self._seed_host = None
             draws, ref_draws = self.host_noise(n, h0, w0, ref=ref_mode)
             self.noise = ops.to_device(draws)
+
+            def add_noise(r, x0, kind, draw, coef, batch, out):
+                r.add_noise_dev(x0, (self.noise_ref if kind else self.noise)[draw], coef, hw0, batch, out)
+
+            def lcm_step(r, eps, cur, draw, coef, batch, nxt, den, dec_in):
+                r.lcm_step_dev(eps, cur, self.noise[draw] if draw else None, coef, hw0, batch, nxt, den, dec_in)
         a = self.arena
         enc_in = a.alloc(B * H * W, 8)
         x0 = a.alloc(B * hw0, 8)
@@ -1320,7 +1335,7 @@ class Engine:
         if ref_mode:
             ref_b = ops.zeros(1, H, W, 3, dtype=torch.uint8)
             self.ref_u8 = ref_b[0]
-            if not device_seed:
+            if ref_draws is not None:
                 self.noise_ref = ops.to_device(ref_draws)
             ref_in, ref_x0, ref_xt, ref_eps = a.alloc(H * W, 8), a.alloc(hw0, 8), a.alloc(hw0, 8), a.alloc(hw0, 8)
             for t in (ref_x0, ref_xt, ref_eps):
@@ -1329,10 +1344,7 @@ class Engine:
             self._encode(r, ref_in, H, W, ref_x0)
             self.buffers["ref_x0"] = ref_x0
         # every frame gets the same draws: the reference resets its RNG per frame
-        if device_seed:
-            r.add_noise_seeded(x0, seeds, 0, 0, c[0:2], hw0, B, lat[0])
-        else:
-            r.add_noise_dev(x0, self.noise[0], c[0:2], hw0, B, lat[0])
+        add_noise(r, x0, 0, 0, c[0:2], B, lat[0])
         mark = a.mark()
         for i in range(n):
             a.rewind(mark)
@@ -1370,10 +1382,7 @@ class Engine:
                 rc = RefCtx(self.ucfg)
                 # ref_xt = add_noise(ref latents, fresh draw, t_i) (lcm_reference_pipeline.py:861-871); the coefficients of
                 # timestep t_i are the first two of the step's scheduler coefficients
-                if device_seed:  # (kind 1: the reference latents' draws, one per step)
-                    r.add_noise_seeded(ref_x0, seeds, 1, i, c[2 + 6 * i:4 + 6 * i], hw0, 1, ref_xt)
-                else:
-                    r.add_noise_dev(ref_x0, self.noise_ref[i], c[2 + 6 * i:4 + 6 * i], hw0, 1, ref_xt)
+                add_noise(r, ref_x0, 1, i, c[2 + 6 * i:4 + 6 * i], 1, ref_xt)  # (kind 1: the reference latents' draws, one per step)
                 w_mid, w_skips = self._unet_encoder(r, i, ref_xt, sizes, ref=rc, temb=self.shared["temb"]["ref"])
                 self._unet_decoder(r, i, w_mid, w_skips, sizes, ref_eps, ref=rc, temb=self.shared["temb"]["ref"])
                 rc.mode = "read"
@@ -1382,12 +1391,8 @@ class Engine:
                 u_mid, u_skips = self._unet_encoder(r, i, cur, sizes)
             self._unet_decoder(r, i, u_mid, u_skips, sizes, eps, ref=rc if ref_mode else None)
             last = i == n - 1
-            if device_seed:  # (draw i + 1 = today's noise[i + 1]; 0: a one-step schedule adds none)
-                r.lcm_step_seeded(eps, cur, seeds, 0, i + 1 if sched.multistep else 0, c[2 + 6 * i:8 + 6 * i], hw0, B, nxt, den,
-                                  dec_in if last else None)
-            else:
-                nz = self.noise[i + 1] if sched.multistep else None
-                r.lcm_step_dev(eps, cur, nz, c[2 + 6 * i:8 + 6 * i], hw0, B, nxt, den, dec_in if last else None)
+            # (draw i + 1; 0: a one-step schedule adds none)
+            lcm_step(r, eps, cur, i + 1 if sched.multistep else 0, c[2 + 6 * i:8 + 6 * i], B, nxt, den, dec_in if last else None)
         self._decode(r, dec_in, h0, w0, dec_out)
         r.postprocess_rgb(dec_out, 8, B * H * W, out_b)
         # program: what a lone launch runs (the ControlNet encoder on the side stream when `overlap_controlnet`);
