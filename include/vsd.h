@@ -311,6 +311,43 @@ typedef struct vsd_prompt_seg {
 } vsd_prompt_seg;
 int vsd_prompt_install(vsd_ctx* ctx, const void* src_block, void* dst_block, const vsd_prompt_seg* segs_dev, int nseg, int frame, void* stream);
 
+/* ---- per-frame options: strength and ControlNet scale per frame of one launch (csrc/noise.hip, csrc/norm.hip, csrc/frame_options.hip) ----
+ * `strength` decides the timesteps (scheduler coefficients, time embeddings) and `controlnet_scale` the 13 residual scales.  The default
+ * program reads one set of each per PLAN; a program recorded with Engine.prepare(frame_options=True) reads them per FRAME of the launch
+ * through the four entry points below.  None of them is a plan function (VSD_VERSION and the plan format are unchanged).
+ * vsd_add_noise_frames / vsd_lcm_step_frames: the scheduler kernels (THE SCHEDULER ARITHMETIC above, the same two bodies) with image b
+ *   reading its coefficients at (const float*)coef_dev + b * coef_stride ({sqrt_a, sqrt_b}: coef_stride >= 2; the six of vsd_lcm_step:
+ *   coef_stride >= 6).  The noise is the shared table noise_f32 (fp32 [4][hw]) or per-image seeds (seeds_dev, kind, draw: THE NOISE
+ *   CONTRACT): add_noise takes exactly one of the two; lcm_step at most one, and both NULL means the step adds no noise (seeded noise
+ *   needs draw >= 1).  Image b's output is bit for bit vsd_add_noise_dev / _seeded (vsd_lcm_step_dev / _seeded) with batch = 1 on image
+ *   b's rows, image b's seed and image b's coefficients.
+ * vsd_groupnorm_addvec: vsd_groupnorm_batched of ONE source tensor with a per-image vector added to its input: image b normalises
+ *   fp32(x[b][row][ch]) + fp32(addvec[b * ld_addvec + ch]) -- statistics and output are both of that fp32 sum, which is never rounded to
+ *   fp16.  addvec: fp16, 16-byte aligned, ld_addvec (halfs between two images' vectors) a non-negative multiple of 8.  The kernels are
+ *   vsd_groupnorm_batched's bodies instantiated with the vector (same launch forms: vsd_groupnorm_launches, same workspace, same order of
+ *   every sum): a zero vector gives vsd_groupnorm_batched's bits, and so does an x + vector that fp16 holds exactly.  In a frame_options program it is norm2 of every ResnetBlock: conv1 is recorded without its `rowvec` and
+ *   norm2 adds the frame's slice of the time table (which carries conv1's bias) instead.
+ * vsd_cn_merge_frames: ONE launch for all ControlNet merges of a step.  segs_dev: nseg (1..VSD_MERGE_SEG_MAX) segments in DEVICE memory,
+ *   16-byte aligned; segment j names fp16 tensors of [batch * rows][channels] by ADDRESS (z: the zero-conv's output, recorded with
+ *   out_scale = 1 and no residual; u: the UNet tensor; out), its rows per image, channels (a multiple of 8) and scale column col.  For every
+ *   image b, row and channel:  out = fp16(fp32 fma(fp32(z), scales_dev[b * scale_stride + col], fp32(u))) -- one fp32 fma, then one
+ *   rounding to fp16.  out may alias z or u.  16-byte loads and stores.  A table is read back and checked when the context first sees it
+ *   (one blocking copy; the engine's prepare) and must not change afterwards; nseg = 0 makes the context forget the table at segs_dev.
+ *   VSD_ERR_ARG with a reason, BEFORE anything is launched: nseg outside 1..VSD_MERGE_SEG_MAX, batch outside 1..65535, a misaligned
+ *   table / address / scales_dev, channels no multiple of 8, rows < 1, a scale column outside [0, scale_stride).  The tensors' SIZES are
+ *   the caller's. */
+#define VSD_MERGE_SEG_MAX 16
+typedef struct vsd_merge_seg {
+  int64_t z, u, out, rows, channels, col;
+} vsd_merge_seg;
+int vsd_add_noise_frames(vsd_ctx* ctx, const void* x0, const void* noise_f32, const void* seeds_dev, int kind, int draw, const void* coef_dev,
+                         int coef_stride, int hw, int batch, void* out, void* stream);
+int vsd_lcm_step_frames(vsd_ctx* ctx, const void* eps, const void* sample, const void* noise_f32, const void* seeds_dev, int kind, int draw,
+                        const void* coef_dev, int coef_stride, int hw, int batch, void* prev, void* denoised, void* dec_in, void* stream);
+int vsd_groupnorm_addvec(vsd_ctx* ctx, const void* src, const void* addvec, int ld_addvec, int c, int hw, int batch, int groups, float eps,
+                         const void* gamma, const void* beta, int silu, void* out, void* workspace, void* stream);
+int vsd_cn_merge_frames(vsd_ctx* ctx, const vsd_merge_seg* segs_dev, int nseg, const void* scales_dev, int scale_stride, int batch, void* stream);
+
 /* AdaIN of the reference-only mode (lcm_reference_pipeline.py:593-603, dead at v2 but still exposed as `ref`):
  * out[r][c] = (x[r][c] - mean_c) / std_c * std_ref_c + mean_ref_c, statistics over the `rows` pixels of one image,
  * population variance clamped at eps before the square root.  stats / stats_ref: fp32 [c][2] per-channel (sum, sum of

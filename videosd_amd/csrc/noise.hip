@@ -1,6 +1,6 @@
 // The scheduler arithmetic and the seeded noise that can feed it (include/vsd.h: THE SCHEDULER ARITHMETIC, THE NOISE CONTRACT).
-// One add_noise body and one lcm_step body serve all six entry points: vsd_add_noise / vsd_lcm_step (coefficients by value, one image),
-// the _dev forms (coefficients in device memory, a batch per launch: a captured graph follows a new strength by rewriting the floats)
+// One add_noise body and one lcm_step body serve all eight entry points: vsd_add_noise / vsd_lcm_step (coefficients by value, one image),
+// the _frames forms (coefficients in device memory PER IMAGE of the launch, either noise source: per-frame options), the _dev forms (coefficients in device memory, a batch per launch: a captured graph follows a new strength by rewriting the floats)
 // and the _seeded forms (the noise table replaced by per-image seeds in device memory: a captured graph follows a new seed per frame
 // with an 8-byte copy per image, nothing re-captured).  The normal draws of a frame are a pure function of (seed, kind, draw, pixel,
 // channel) -- Philox4x32-10, one block per latent pixel = its four channels, Box-Muller in fp32 -- evaluated in the thread that uses
@@ -86,20 +86,30 @@ struct SeededNoise {
   __device__ Normal4 operator()(int, uint32_t image, uint32_t i) const { return seeded_normals(seeds[2 * image], seeds[2 * image + 1], kind, draw, i); }
 };
 
-// Where the coefficients {sa, sb, cskip, cout, sap, sbp} come from: the first N of them by value (add_noise takes two, a step six), or
-// floats in device memory (`const float*`; add_noise reads the first two alone).
+// Where the coefficients {sa, sb, cskip, cout, sap, sbp} come from: the first N of them by value (add_noise takes two, a step six),
+// floats in device memory (`const float*`; add_noise reads the first two alone), or floats in device memory PER IMAGE of the launch
+// (FrameCoef: image b reads base + b * stride).  coef_of(source, image) is what the bodies index; the first two ignore the image.
 template <int N>
 struct CoefValues {
   float v[N];
   __device__ float operator[](int j) const { return v[j]; }
 };
+struct FrameCoef {
+  const float* __restrict__ base;
+  int stride;  // floats between two images' coefficients
+};
+template <int N>
+__device__ __forceinline__ const CoefValues<N>& coef_of(const CoefValues<N>& k, uint32_t) { return k; }
+__device__ __forceinline__ const float* coef_of(const float* k, uint32_t) { return k; }
+__device__ __forceinline__ const float* coef_of(const FrameCoef& k, uint32_t image) { return k.base + (size_t)image * k.stride; }
 
 // THE SCHEDULER ARITHMETIC, per channel 0..3 in fp32 (channels 4..7 are written as zero); blockIdx.y = image of the launch:
 //   out = fp16(fma(sa, x, sb * n))
 template <class Noise, class Coef>
-__global__ void add_noise_kernel(const half_t* __restrict__ x0, Noise noise, Coef k, int hw, half_t* __restrict__ out) {
+__global__ void add_noise_kernel(const half_t* __restrict__ x0, Noise noise, Coef coef, int hw, half_t* __restrict__ out) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= hw) return;
+  const auto& k = coef_of(coef, blockIdx.y);
   const float sa = k[0], sb = k[1];
   const Normal4 nz = noise(hw, blockIdx.y, (uint32_t)i);
   const size_t row = (size_t)blockIdx.y * hw + i;
@@ -113,10 +123,11 @@ __global__ void add_noise_kernel(const half_t* __restrict__ x0, Noise noise, Coe
 //   px0 = fma(-sb, e, xs) / sa;  d = fma(cskip, xs, cout * px0);  den = fp16(d);
 //   prev = fp16(sap * d + sbp * n) as mul, mul, add (NOISE = false, the step that adds none: prev = den);  dec_in = fp16(tanhf(den / 3) * 3)
 template <bool NOISE, class Noise, class Coef>
-__global__ void lcm_step_kernel(const half_t* __restrict__ eps, const half_t* __restrict__ sample, Noise noise, Coef k, int hw,
+__global__ void lcm_step_kernel(const half_t* __restrict__ eps, const half_t* __restrict__ sample, Noise noise, Coef coef, int hw,
                                 half_t* __restrict__ prev, half_t* __restrict__ den, half_t* __restrict__ dec_in) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= hw) return;
+  const auto& k = coef_of(coef, blockIdx.y);
   const float sa = k[0], sb = k[1], cskip = k[2], cout = k[3], sap = k[4], sbp = k[5];
   Normal4 nz = {{0.f, 0.f, 0.f, 0.f}};
   if (NOISE) nz = noise(hw, blockIdx.y, (uint32_t)i);
@@ -229,5 +240,42 @@ extern "C" int vsd_lcm_step_seeded(vsd_ctx* ctx, const void* eps, const void* sa
   LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
   launch_lcm_step(s, eps, sample, draw > 0, SeededNoise{(const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw}, (const float*)coef_dev, hw, batch,
                   prev, denoised, dec_in);
+  return ls.finish();
+}
+
+// ---- coefficients per image of the launch (include/vsd.h: per-frame options): the same two bodies, the coefficient source indexed by image
+extern "C" int vsd_add_noise_frames(vsd_ctx* ctx, const void* x0, const void* noise_f32, const void* seeds_dev, int kind, int draw,
+                                    const void* coef_dev, int coef_stride, int hw, int batch, void* out, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!x0 || !coef_dev || !out || hw <= 0 || batch < 1 || batch > 65535 || coef_stride < 2 || ((uintptr_t)coef_dev & 3))
+    return vsd_fail(ctx, VSD_ERR_ARG, "add_noise_frames: bad arguments (hw >= 1, batch 1..65535, coef_stride >= 2)");
+  if ((noise_f32 != nullptr) == (seeds_dev != nullptr))
+    return vsd_fail(ctx, VSD_ERR_ARG, "add_noise_frames: exactly one of noise_f32 and seeds_dev must be given");
+  if (seeds_dev && (kind < 0 || draw < 0)) return vsd_fail(ctx, VSD_ERR_ARG, "add_noise_frames: kind=%d draw=%d", kind, draw);
+  hipStream_t s = (hipStream_t)stream;
+  const FrameCoef k{(const float*)coef_dev, coef_stride};
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  if (noise_f32)
+    launch_add_noise(s, x0, TableNoise{(const float*)noise_f32}, k, hw, batch, out);
+  else
+    launch_add_noise(s, x0, SeededNoise{(const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw}, k, hw, batch, out);
+  return ls.finish();
+}
+
+extern "C" int vsd_lcm_step_frames(vsd_ctx* ctx, const void* eps, const void* sample, const void* noise_f32, const void* seeds_dev, int kind,
+                                   int draw, const void* coef_dev, int coef_stride, int hw, int batch, void* prev, void* denoised, void* dec_in,
+                                   void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!eps || !sample || !coef_dev || hw <= 0 || batch < 1 || batch > 65535 || coef_stride < 6 || ((uintptr_t)coef_dev & 3))
+    return vsd_fail(ctx, VSD_ERR_ARG, "lcm_step_frames: bad arguments (hw >= 1, batch 1..65535, coef_stride >= 6)");
+  if (noise_f32 && seeds_dev) return vsd_fail(ctx, VSD_ERR_ARG, "lcm_step_frames: at most one of noise_f32 and seeds_dev may be given");
+  if (seeds_dev && (kind < 0 || draw < 1)) return vsd_fail(ctx, VSD_ERR_ARG, "lcm_step_frames: seeded noise needs kind >= 0 and draw >= 1, got %d, %d", kind, draw);
+  hipStream_t s = (hipStream_t)stream;
+  const FrameCoef k{(const float*)coef_dev, coef_stride};
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  if (seeds_dev)
+    launch_lcm_step(s, eps, sample, true, SeededNoise{(const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw}, k, hw, batch, prev, denoised, dec_in);
+  else
+    launch_lcm_step(s, eps, sample, noise_f32 != nullptr, TableNoise{(const float*)noise_f32}, k, hw, batch, prev, denoised, dec_in);
   return ls.finish();
 }

@@ -6,6 +6,8 @@
 // order (deterministic, no atomics), `gn_apply` folds the partials, then streams y = x*a[c] + b[c]
 // (+SiLU).  The input may be the channel concat of two tensors (UNet up blocks) and the output is the
 // concatenated, normalised tensor.  Algorithmic bytes: 2 reads + 1 write of hw*C fp16.
+// vsd_groupnorm_addvec: the same kernels normalising x + a per-image vector (GnParams::addvec; every body is instantiated with and
+// without it, so that a launch without a vector runs the instruction stream it always ran).
 #include <stdarg.h>
 #include <stdlib.h>
 
@@ -29,6 +31,10 @@ struct GnParams {
   int nblk;     // stats workgroups (per image)
   int rpp;      // rows per pass = blockDim / c8
   int batch;    // images stacked along the rows (blockIdx.y): each normalised with its own statistics
+  // vsd_groupnorm_addvec: image b normalises fp32(x) + fp32(addvec[b * ld_addvec + channel]) (the sum is never rounded to fp16); null: x
+  // alone.  The kernels are instantiated for both cases (AV): with a null pointer the launch runs the instruction stream it always ran.
+  const half_t* addvec;
+  int ld_addvec;
   VSD_CUT_FIELD
 };
 
@@ -41,6 +47,7 @@ __device__ __forceinline__ half8 gn_load(const GnParams& p, int row, int ch8) {
 // Both kernels are latency- rather than bandwidth-bound at these sizes (a few MB, L2 resident): every thread issues
 // its row loads four at a time before consuming them, and the partial folds are spread over all threads with every
 // load of a thread independent of the others, so each phase costs about one memory round trip.
+template <bool AV>
 __device__ __forceinline__ void gn_stats_body(const GnParams& p) {
   VSD_CUT(VSD_CUT_GROUPNORM, p.cut)
   extern __shared__ float sm[];  // [16 planes][threads] per-thread channel sums (see below), folded in a fixed order
@@ -54,6 +61,14 @@ __device__ __forceinline__ void gn_stats_body(const GnParams& p) {
   float s[8], q[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) s[i] = q[i] = 0.f;
+  // the image's vector: this thread's eight channels, loaded once
+  constexpr bool av = AV;
+  float af[8];
+  if (av) {
+    const half8 a8 = *reinterpret_cast<const half8*>(p.addvec + (size_t)blockIdx.y * p.ld_addvec + ch8 * 8);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) af[i] = (float)a8[i];
+  }
   // rows in batches of four PREDICATED loads (an out-of-range row re-reads the block's first row and is masked to zero):
   // every batch is one memory round trip, the ragged tail included -- a per-row tail loop pays one round trip per row
   const half8 zero8 = (half8){0, 0, 0, 0, 0, 0, 0, 0};
@@ -67,6 +82,12 @@ __device__ __forceinline__ void gn_stats_body(const GnParams& p) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float v0 = (float)x0[i], v1 = (float)x1[i], v2 = (float)x2[i], v3 = (float)x3[i];
+      if (av) {  // (a masked row stays zero)
+        v0 += af[i];
+        v1 = ok1 ? v1 + af[i] : 0.f;
+        v2 = ok2 ? v2 + af[i] : 0.f;
+        v3 = ok3 ? v3 + af[i] : 0.f;
+      }
       s[i] += v0; q[i] += v0 * v0;
       s[i] += v1; q[i] += v1 * v1;
       s[i] += v2; q[i] += v2 * v2;
@@ -109,10 +130,13 @@ __device__ __forceinline__ void gn_stats_body(const GnParams& p) {
   }
 }
 
-__global__ void gn_stats_kernel(const GnParams p) { gn_stats_body(p); }
+template <bool AV>
+__global__ void gn_stats_kernel(const GnParams p) { gn_stats_body<AV>(p); }
 // (two tensors as one grid: common.h launch_pairable; blockIdx.z = which)
-__global__ void gn_stats_pair_kernel(const Pair<GnParams> g) { gn_stats_body(g.p[blockIdx.z]); }
+template <bool AV>
+__global__ void gn_stats_pair_kernel(const Pair<GnParams> g) { gn_stats_body<AV>(g.p[blockIdx.z]); }
 
+template <bool AV>
 __device__ __forceinline__ void gn_apply_body(const GnParams& p) {
   VSD_CUT(VSD_CUT_GROUPNORM, p.cut)
   extern __shared__ float sm[];  // [groups][2] mean, rstd | [nch][groups*2] partial folds
@@ -133,6 +157,13 @@ __device__ __forceinline__ void gn_apply_body(const GnParams& p) {
   half8 xf2 = gn_load(p, okf2 ? rf + 2 * p.rpp : rsafe, ch8), xf3 = gn_load(p, okf3 ? rf + 3 * p.rpp : rsafe, ch8);
   const half8 ga = *reinterpret_cast<const half8*>(p.gamma + ch8 * 8);
   const half8 be = *reinterpret_cast<const half8*>(p.beta + ch8 * 8);
+  constexpr bool av = AV;
+  float af[8];
+  if (av) {
+    const half8 a8 = *reinterpret_cast<const half8*>(p.addvec + (size_t)blockIdx.y * p.ld_addvec + ch8 * 8);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) af[i] = (float)a8[i];
+  }
   {
     // fold the statistics partials: (pair, chunk) per thread, chunk ch sums blocks ch, ch+nch, ... (16 loads at a time,
     // all independent), then the chunks are added in order: deterministic
@@ -185,7 +216,9 @@ __device__ __forceinline__ void gn_apply_body(const GnParams& p) {
     half8 y;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      float v = (float)x[i] * a[i] + b[i];
+      float xv = (float)x[i];
+      if (av) xv += af[i];
+      float v = xv * a[i] + b[i];
       if (p.silu) v = silu_f(v);
       y[i] = (half_t)v;
     }
@@ -205,8 +238,10 @@ __device__ __forceinline__ void gn_apply_body(const GnParams& p) {
     if (ok3) norm_store(r + 3 * p.rpp, x3);
   }
 }
-__global__ void gn_apply_kernel(const GnParams p) { gn_apply_body(p); }
-__global__ void gn_apply_pair_kernel(const Pair<GnParams> g) { gn_apply_body(g.p[blockIdx.z]); }
+template <bool AV>
+__global__ void gn_apply_kernel(const GnParams p) { gn_apply_body<AV>(p); }
+template <bool AV>
+__global__ void gn_apply_pair_kernel(const Pair<GnParams> g) { gn_apply_body<AV>(g.p[blockIdx.z]); }
 
 // ------------------------------------------------------------------ one-launch GroupNorm for small images
 // One workgroup per (image, group): the group's cpg channels of every pixel (a cpg*2-byte piece of each NHWC row) are
@@ -217,7 +252,7 @@ __global__ void gn_apply_pair_kernel(const Pair<GnParams> g) { gn_apply_body(g.p
 // GPW = groups per workgroup (1 in every shipped instantiation).  Round 5 measured 2 groups of 20 channels / 4 of 10 per workgroup
 // (80-byte row pieces, 16-byte vectors, half the workgroups) at 32 x 32 x 640: 9.6 against 8.3 us for one image, 12.5 against 13.2 for
 // five (scripts/gn_bench.py) -- the kernel is launch + dependent round trips, not line traffic: not used.
-template <int VW, int NV, int RMAX, int GPW = 1>
+template <int VW, int NV, int RMAX, bool AV, int GPW = 1>
 __device__ __forceinline__ void gn_fused_body(const GnParams& p) {
   VSD_CUT(VSD_CUT_GROUPNORM, p.cut)
   typedef _Float16 vec_t __attribute__((ext_vector_type(VW)));
@@ -251,6 +286,13 @@ __device__ __forceinline__ void gn_fused_body(const GnParams& p) {
     gav[v] = *reinterpret_cast<const vec_t*>(p.gamma + ch0 + v * VW);
     bev[v] = *reinterpret_cast<const vec_t*>(p.beta + ch0 + v * VW);
   }
+  // the image's vector: this workgroup's group of channels, loaded once per thread with the rows
+  constexpr bool av = AV;
+  vec_t adv[NV];
+  if (av) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) adv[v] = *reinterpret_cast<const vec_t*>(p.addvec + (size_t)blockIdx.y * p.ld_addvec + ch0 + v * VW);
+  }
 #pragma unroll
   for (int r = 0; r < RMAX; ++r) {
     const int row = t + r * T;
@@ -259,7 +301,8 @@ __device__ __forceinline__ void gn_fused_body(const GnParams& p) {
       for (int v = 0; v < NV; ++v)
 #pragma unroll
         for (int i = 0; i < VW; ++i) {
-          const float f = (float)x[r][v][i];
+          float f = (float)x[r][v][i];
+          if (av) f += (float)adv[v][i];
           s[(v * VW + i) / CPG] += f;
           q[(v * VW + i) / CPG] += f * f;
         }
@@ -314,7 +357,9 @@ __device__ __forceinline__ void gn_fused_body(const GnParams& p) {
         vec_t y;
 #pragma unroll
         for (int i = 0; i < VW; ++i) {
-          float f = (float)x[r][v][i] * a[v][i] + b[v][i];
+          float xv = (float)x[r][v][i];
+          if (av) xv += (float)adv[v][i];
+          float f = xv * a[v][i] + b[v][i];
           if (p.silu) f = silu_f(f);
           y[i] = (half_t)f;
         }
@@ -326,13 +371,13 @@ __device__ __forceinline__ void gn_fused_body(const GnParams& p) {
 
 // (groups of more than 20 channels run on images of at most 256 pixels -- gn_try_fused -- i.e. at most 256 threads: said here,
 //  the 40-channel form keeps its row, gamma and beta in registers; under the default 1024-thread bound it had 128 and spilled 18)
-template <int VW, int NV, int RMAX>
+template <int VW, int NV, int RMAX, bool AV>
 __global__ __launch_bounds__(VW * NV > 20 ? 256 : 1024) void gn_fused_kernel(const GnParams p) {
-  gn_fused_body<VW, NV, RMAX>(p);
+  gn_fused_body<VW, NV, RMAX, AV>(p);
 }
-template <int VW, int NV, int RMAX>
+template <int VW, int NV, int RMAX, bool AV>
 __global__ __launch_bounds__(VW * NV > 20 ? 256 : 1024) void gn_fused_pair_kernel(const Pair<GnParams> g) {
-  gn_fused_body<VW, NV, RMAX>(g.p[blockIdx.z]);
+  gn_fused_body<VW, NV, RMAX, AV>(g.p[blockIdx.z]);
 }
 
 // launches the one-kernel form when the shape fits it (dry: only says whether it would); returns false otherwise
@@ -348,7 +393,10 @@ static bool gn_try_fused(vsd_ctx* ctx, const GnParams& p, int batch, hipStream_t
 #define GN_GO(VW_, NV_)                                                                           \
   {                                                                                               \
     if (dry) return true;                                                                         \
-    launch_pairable(ctx, gn_fused_kernel<VW_, NV_, 1>, gn_fused_pair_kernel<VW_, NV_, 1>, grid, block, 0, s, p); /* threads >= hw: one row per thread */ \
+    if (p.addvec)                                                                                 \
+      launch_pairable(ctx, gn_fused_kernel<VW_, NV_, 1, true>, gn_fused_pair_kernel<VW_, NV_, 1, true>, grid, block, 0, s, p); \
+    else                                                                                          \
+      launch_pairable(ctx, gn_fused_kernel<VW_, NV_, 1, false>, gn_fused_pair_kernel<VW_, NV_, 1, false>, grid, block, 0, s, p); /* threads >= hw: one row per thread */ \
     return true;                                                                                  \
   }
   if (a8 && p.cpg == 40) GN_GO(8, 5)
@@ -439,16 +487,35 @@ extern "C" int vsd_groupnorm(vsd_ctx* ctx, const void* src0, const void* src1, i
   return vsd_groupnorm_batched(ctx, src0, src1, c0, c1, hw, 1, groups, eps, gamma, beta, silu, out, workspace, stream);
 }
 
+static int gn_run(vsd_ctx* ctx, const void* src0, const void* src1, int c0, int c1, int hw, int batch, int groups, float eps, const void* gamma,
+                  const void* beta, int silu, void* out, void* workspace, void* stream, const void* addvec, int ld_addvec);
+
 extern "C" int vsd_groupnorm_batched(vsd_ctx* ctx, const void* src0, const void* src1, int c0, int c1, int hw, int batch,
                                      int groups, float eps, const void* gamma, const void* beta, int silu, void* out,
                                      void* workspace, void* stream) {
   if (!ctx) return VSD_ERR_ARG;
+  return gn_run(ctx, src0, src1, c0, c1, hw, batch, groups, eps, gamma, beta, silu, out, workspace, stream, nullptr, 0);
+}
+
+// GroupNorm of x + a per-image vector (include/vsd.h): the kernels of vsd_groupnorm_batched with GnParams::addvec set
+extern "C" int vsd_groupnorm_addvec(vsd_ctx* ctx, const void* src, const void* addvec, int ld_addvec, int c, int hw, int batch, int groups,
+                                    float eps, const void* gamma, const void* beta, int silu, void* out, void* workspace, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!addvec || ((uintptr_t)addvec & 15) || ld_addvec < 0 || ld_addvec % 8)
+    return vsd_fail(ctx, VSD_ERR_ARG, "groupnorm_addvec: addvec must be a 16-byte aligned pointer, ld_addvec=%d a non-negative multiple of 8", ld_addvec);
+  return gn_run(ctx, src, nullptr, c, 0, hw, batch, groups, eps, gamma, beta, silu, out, workspace, stream, addvec, ld_addvec);
+}
+
+static int gn_run(vsd_ctx* ctx, const void* src0, const void* src1, int c0, int c1, int hw, int batch, int groups, float eps, const void* gamma,
+                  const void* beta, int silu, void* out, void* workspace, void* stream, const void* addvec, int ld_addvec) {
 #ifdef VSD_PROBE
   { static const bool skip = getenv("VSD_SKIP_GN") != nullptr; if (skip) return VSD_OK; }  // (what-if probe builds only)
 #endif
   if (batch < 1 || batch > 65535) return vsd_fail(ctx, VSD_ERR_ARG, "groupnorm: batch=%d", batch);
   GnParams p;
   p.batch = batch;
+  p.addvec = (const half_t*)addvec;
+  p.ld_addvec = ld_addvec;
   VSD_CUT_SET(p)
   p.src0 = (const half_t*)src0;
   p.src1 = (const half_t*)src1;
@@ -489,7 +556,10 @@ extern "C" int vsd_groupnorm_batched(vsd_ctx* ctx, const void* src0, const void*
   {
     const size_t smem_stats = (size_t)p.rpp * p.c * 2 * sizeof(float);
     LaunchScope ls(ctx, s, VSD_FAM_GROUPNORM, 0.0);
-    launch_pairable(ctx, gn_stats_kernel, gn_stats_pair_kernel, dim3(nblk, batch), dim3(threads), (unsigned)smem_stats, s, p);
+    if (p.addvec)
+      launch_pairable(ctx, gn_stats_kernel<true>, gn_stats_pair_kernel<true>, dim3(nblk, batch), dim3(threads), (unsigned)smem_stats, s, p);
+    else
+      launch_pairable(ctx, gn_stats_kernel<false>, gn_stats_pair_kernel<false>, dim3(nblk, batch), dim3(threads), (unsigned)smem_stats, s, p);
     int rc = ls.finish();
     if (rc) return rc;
   }
@@ -498,7 +568,10 @@ extern "C" int vsd_groupnorm_batched(vsd_ctx* ctx, const void* src0, const void*
     static const int ablk_cap = getenv("VSD_GN_ABLK") ? atoi(getenv("VSD_GN_ABLK")) : 256;  // (benchmarking: apply workgroups per image)
     if (ablk > ablk_cap) ablk = ablk_cap;
     LaunchScope ls(ctx, s, VSD_FAM_GROUPNORM, 0.0);
-    launch_pairable(ctx, gn_apply_kernel, gn_apply_pair_kernel, dim3(ablk, batch), dim3(threads), (unsigned)smem, s, p);
+    if (p.addvec)
+      launch_pairable(ctx, gn_apply_kernel<true>, gn_apply_pair_kernel<true>, dim3(ablk, batch), dim3(threads), (unsigned)smem, s, p);
+    else
+      launch_pairable(ctx, gn_apply_kernel<false>, gn_apply_pair_kernel<false>, dim3(ablk, batch), dim3(threads), (unsigned)smem, s, p);
     return ls.finish();
   }
 }

@@ -332,14 +332,26 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
     # ... and one whose PROMPT is per frame inside a launch (VideoSDPipeline(frame_prompts=True)) likewise: frames of sessions that differ in
     # `prompt` share a launch, which gets `prompts`, one per frame in request order (`prompt` stays the first request's).
     per_prompt = bool(getattr(pipe, "per_frame_prompt", False))
-    per_frame = tuple(k for k, on in (("seed", per_seed), ("prompt", per_prompt)) if on)
+    # ... and one whose `strength` / `controlnet_scale` are per frame inside a launch (VideoSDPipeline(frame_options=True)): frames of sessions
+    # whose sliders stand differently share a launch when the pipeline puts them in one `option_class` (the number of timesteps: the
+    # program's length); the launch gets both as lists, one per frame in request order.  A request with other values never waits for the
+    # lanes to drain (the pipeline's `needs_idle` says so).
+    per_opts = bool(getattr(pipe, "per_frame_options", False)) and hasattr(pipe, "option_class")
+    per_frame = tuple(k for k, on in (("seed", per_seed), ("prompt", per_prompt), ("strength", per_opts), ("controlnet_scale", per_opts)) if on)
 
     def same_options(a, b):
         if not per_frame:
             return a == b
-        return {k: v for k, v in a.items() if k not in per_frame} == {k: v for k, v in b.items() if k not in per_frame}
+        if {k: v for k, v in a.items() if k not in per_frame} != {k: v for k, v in b.items() if k not in per_frame}:
+            return False
+        if per_opts and a != b:
+            try:
+                return pipe.option_class(a) == pipe.option_class(b)
+            except Exception:
+                return False
+        return True
 
-    def launch_options(kwargs, seeds, prompts):
+    def launch_options(kwargs, seeds, prompts, opts=()):
         if not per_frame:
             return kwargs
         kw = dict(kwargs)
@@ -347,6 +359,9 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
             kw["seed"] = list(seeds)
         if per_prompt:
             kw["prompts"] = list(prompts)
+        if per_opts:
+            kw["strength"] = [o[0] for o in opts]
+            kw["controlnet_scale"] = [o[1] for o in opts]
         return kw
 
     backlog, inflight, lane = [], [], 0
@@ -557,6 +572,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
         group_ = [(rid, args, slot)]
         seeds_ = [kwargs.get("seed", 42)]  # (`infer`'s default)
         prompts_ = [kwargs.get("prompt", ["pixar, cg"])]  # (likewise)
+        opts_ = [(kwargs.get("strength", 0.4), kwargs.get("controlnet_scale", 1))]  # (likewise)
         batchable = max_batch > 1 and method == "infer" and len(args) == 1 and hasattr(pipe, "infer_batch")
         if batchable and hasattr(pipe, "can_batch"):
             try:
@@ -582,6 +598,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
                     group_.append((r2, a2, s2))
                     seeds_.append(_k.get("seed", 42))
                     prompts_.append(_k.get("prompt", ["pixar, cg"]))
+                    opts_.append((_k.get("strength", 0.4), _k.get("controlnet_scale", 1)))
                 else:  # different options / another method / shutdown: serve it next, stop growing this batch
                     backlog.insert(0, nxt)
                     break
@@ -598,7 +615,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
             busy = {e[4] for e in inflight}
             lane = next(l for l in range(lanes) if l not in busy)
             try:
-                handle = pipe.submit_batch([a[0] for _, a, _s in group_], lane=lane, **launch_options(kwargs, seeds_, prompts_))
+                handle = pipe.submit_batch([a[0] for _, a, _s in group_], lane=lane, **launch_options(kwargs, seeds_, prompts_, opts_))
             except BaseException as e:
                 drain()
                 fail(group_, e)
@@ -610,7 +627,7 @@ def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1,
         drain()  # anything else runs alone, after what is in flight
         try:
             if len(group_) > 1:
-                outs = pipe.infer_batch([a[0] for _, a, _s in group_], **launch_options(kwargs, seeds_, prompts_))
+                outs = pipe.infer_batch([a[0] for _, a, _s in group_], **launch_options(kwargs, seeds_, prompts_, opts_))
                 for (r, _a, s), o in zip(group_, outs):
                     reply(r, o, s)
                 stats.add(len(group_), (time.time() - t_in) * 1e3)

@@ -405,6 +405,61 @@ def prompt_segments(src: PromptLayout, dst: FramePromptLayout):
     return segs
 
 
+class OptionLayout:
+    """Byte layout of the constants that depend on a frame's OPTIONS (`Engine.prepare(frame_options=True)`) for `frames` frames: per item a
+    run of `frames` slots of equal size, frame f owning bytes [off + f * size, off + (f + 1) * size) --
+      "coef": fp32 [coef_stride]: [0:2] the add_noise coefficients, [2 + 6i : 8 + 6i] the scheduler coefficients of step i (the layout of
+              the default program's constant block), padded to whole 16-byte units;
+      one item per network ("unet", "cn"): fp16 [n][cols], its per-step time-embedding projections (conv1's bias folded in).
+    frames = 1 is the layout of an option ENTRY (one schedule's constants, a cache entry); an engine's own block has its batch size.  Every
+    offset and size is a multiple of 16 bytes: a slot is installed by `prompt_install`, a segmented copy of 16-byte chunks."""
+
+    def __init__(self, n: int, cols: Dict[str, int], frames: int):
+        self.n, self.frames, self.cols = int(n), int(frames), dict(cols)
+        self.coef_stride = _ru(2 + 6 * self.n, 4)  # floats
+        self.items = {}  # name -> (offset, bytes per frame)
+        off = 0
+        for name, nb in [("coef", self.coef_stride * 4)] + [(k, self.n * c * 2) for k, c in self.cols.items()]:
+            if nb % 16:
+                raise ValueError(f"frame_options: {name}: {nb} bytes per frame: the time tables' columns must be a multiple of 8")
+            self.items[name] = (off, nb)
+            off = _ru(off + self.frames * nb, 256)
+        self.nbytes = max(off, 256)
+
+    def view(self, buf, name, frame: int = 0):
+        """frame `frame`'s slot of item `name` in `buf` (bytes of this layout): fp32 [coef_stride], or fp16 [n][cols]"""
+        off, nb = self.items[name]
+        raw = buf[off + frame * nb:off + (frame + 1) * nb]
+        return raw.view(torch.float32) if name == "coef" else raw.view(torch.float16).view(self.n, self.cols[name])
+
+
+def option_segments(src: OptionLayout, dst: OptionLayout):
+    """The copy list of `vsd_prompt_install` (include/vsd.h vsd_prompt_seg) that puts an option entry (layout `src`, one frame) into ONE frame
+    slot of an engine's block (layout `dst`): per item one run (src_off, dst_off, 1, bytes, frames * bytes, bytes)."""
+    if src.frames != 1 or src.n != dst.n or src.cols != dst.cols:
+        raise ValueError("an option entry of another schedule length or other networks than the block it is installed into")
+    segs = [(src.items[k][0], doff, 1, nb, dst.frames * nb, nb) for k, (doff, nb) in dst.items.items()]
+    assert all(v % 16 == 0 for sg in segs for v in sg[:2] + sg[3:])
+    return segs
+
+
+class OptionEntry:
+    """One schedule's constants in device memory (layout: OptionLayout with one frame): what every `strength` that gives these timesteps
+    shares.  Engines read THEIR OWN block; an entry is installed into a frame slot by copying."""
+
+    def __init__(self, layout: OptionLayout, buf, timesteps):
+        self.layout, self.buf, self.timesteps = layout, buf, tuple(timesteps)
+
+
+def controlnet_scales(nres: int, controlnet_scale: float):
+    """ControlNetModel guess mode: logspace(-1, 0, nres) * conditioning_scale (always on: lcm_controlnet.py:399,447), fp32"""
+    return torch.logspace(-1, 0, nres) * float(controlnet_scale)
+
+
+FRAME_OPTION_OPS = ("add_noise_frames", "lcm_step_frames", "groupnorm_addvec", "cn_merge_frames", "prompt_install")
+MAX_OPTION_ENTRIES = 64  # (at most 50 timestep tuples per `steps`; an entry is a few hundred KB)
+
+
 class PromptBlock:
     """One prompt's constants in device memory (layout: PromptLayout).  Engines read THEIR OWN block (its addresses are in
     their captured graphs); a cached prompt is installed by copying its block over the engine's."""
@@ -515,6 +570,12 @@ class Engine:
         self.frame_prompts = False
         self._want_list = None  # `use_prompts`: one PromptBlock per frame of the launch (None: `_want` / the default for every frame)
         self._slot_src = []     # the PromptBlock whose K / V^T each frame slot of `pblock` holds (a reference: the source outlives its install)
+        # `prepare(frame_options=True)`: strength / controlnet_scale per frame of the launch (`use_options`)
+        self.frame_options = False
+        self.fo_layout = self.fo_buf = self.fo_scale = self._fo_scale_host = self._fo_scale_last = None
+        self._want_opts = None   # `use_options`: (OptionEntry, controlnet_scale) per frame (None: the plan's own options for every frame)
+        self._opt_slot_src = []  # the OptionEntry each frame slot of `fo_buf` holds
+        self._merge_tabs = []    # the segment tables of the recorded `cn_merge_frames` calls (their addresses are in the graph)
         self.absorb_cross_attention = True  # cross-attention of the wide blocks as two GEMMs (vsd_xattn_fold)
         self.use_fused_tail = True          # 320-wide blocks: per-token chains as fused launches (csrc/fused_tail.hip)
         self.group_merges = not __import__("os").environ.get("VSD_NO_GROUP")  # the ControlNet merges of a step as two grouped launches
@@ -551,6 +612,11 @@ class Engine:
         e._want = None
         e._want_list = None
         e._slot_src = []
+        e.frame_options = False
+        e.fo_layout = e.fo_buf = e.fo_scale = e._fo_scale_host = e._fo_scale_last = None
+        e._want_opts = None
+        e._opt_slot_src = []
+        e._merge_tabs = []
         e.is_slot = bool(share_plan)
         if not share_plan:
             e.shared = {}
@@ -660,6 +726,100 @@ class Engine:
             self.ops.copy_(self.pblock.buf, src.buf)  # one device-to-device copy on this engine's own stream
             self._installed = src
 
+    # ---------------------------------------------------------------- per-frame options
+    def _nres(self) -> int:
+        return 13 if self.cn is None else len(self.cn.zero_convs) + 1
+
+    def _option_cols(self, use_controlnet: bool) -> Dict[str, int]:
+        return {name: net.temb_proj.n for name, net in [("unet", self.unet)] + ([("cn", self.cn)] if use_controlnet else [])}
+
+    def option_entry(self, strength: float, steps: int, use_controlnet: bool = True) -> OptionEntry:
+        """The constants of the schedule `(strength, steps)` as a cache entry, keyed by its TIMESTEPS (`lcm_timesteps` maps many strengths
+        to one tuple): scheduler coefficients and both time tables in one device buffer, built once (~1 ms on the GPU: the ~10 tiny
+        GEMMs of the time path) and kept in an LRU cache every engine of the family shares.  Touches nothing a running launch reads."""
+        from collections import OrderedDict
+
+        sched = LCMSchedule(strength, steps)
+        key = (tuple(int(t) for t in sched.timesteps), bool(use_controlnet))
+        cache = self.family.setdefault("option_entries", OrderedDict())
+        ent = cache.get(key)
+        if ent is None:
+            n = len(sched)
+            lays = self.family.setdefault("option_layouts", {})  # (one layout OBJECT per (steps, networks): the copy lists are per pair)
+            lay = lays.get((n, bool(use_controlnet)))
+            if lay is None:
+                lay = lays[(n, bool(use_controlnet))] = OptionLayout(n, self._option_cols(use_controlnet), 1)
+            buf = self.ops.zeros(lay.nbytes, dtype=torch.uint8)
+            vals = list(sched.add_noise_coef())
+            for i in range(n):
+                vals += [float(x) for x in sched.step_coef(i)]
+            host = torch.zeros(lay.coef_stride, dtype=torch.float32)
+            host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
+            self.ops.upload(lay.view(buf, "coef"), host)
+            for name, net in [("unet", self.unet)] + ([("cn", self.cn)] if use_controlnet else []):
+                self._time_embeddings(net, sched, lay.view(buf, name))
+            self.ops.synchronize()  # (the other lanes' streams read it too)
+            ent = cache[key] = OptionEntry(lay, buf, key[0])
+            self.family["option_builds"] = self.family.get("option_builds", 0) + 1
+            while len(cache) > max(1, int(self.family.get("max_option_entries", MAX_OPTION_ENTRIES))):
+                cache.popitem(last=False)  # least recently used first; an engine (or a launch's handle) that still holds it keeps it alive
+        else:
+            cache.move_to_end(key)
+        return ent
+
+    def use_options(self, pairs):
+        """`frame_options` engines: frame i of this engine's launches runs with pairs[i] = (strength, controlnet_scale) from the next launch
+        on.  Every strength must give the plan's NUMBER of timesteps (another number is another program), else ValueError.  A frame slot
+        whose timesteps changed since this engine's last launch is rewritten by ONE `prompt_install` launch on the engine's own stream ahead
+        of the program; the ControlNet scales go from a pinned mirror with one stream-ordered copy, when any changed.  Unchanged slots cost
+        nothing; nothing is re-captured, nobody waits.  Call it with no launch of THIS engine in flight."""
+        if not self.frame_options or self.plan is None:
+            raise ValueError("use_options needs an engine prepared with frame_options=True (a default plan takes update_options)")
+        pairs = [(float(s), float(c)) for s, c in pairs]
+        B, n, steps = self.plan["batch"], self.plan["n"], self.plan["steps"]
+        if len(pairs) != B:
+            raise ValueError(f"use_options: {len(pairs)} option pair(s) for a launch of {B} frame(s)")
+        from .lcm import lcm_timesteps
+
+        counts = [len(lcm_timesteps(s, steps)) for s, _c in pairs]
+        if any(k != n for k in counts):
+            raise ValueError(f"use_options: every frame of this plan runs {n} timestep(s) (steps={steps}); the strengths "
+                             f"{[s for s, _c in pairs]} give {counts}: another number of timesteps is another program")
+        self._want_opts = [(self.option_entry(s, steps, self.plan["cn"]), c) for s, c in pairs]
+
+    def _opt_seg_table(self, src: OptionLayout, dst: OptionLayout):
+        """(device table, segments) of `prompt_install` for this pair of option layouts: built once per family"""
+        tabs = self.family.setdefault("opt_seg_tables", {})
+        got = tabs.get((src, dst))
+        if got is None:
+            segs = option_segments(src, dst)
+            got = tabs[(src, dst)] = (self.ops.to_device(torch.tensor(segs, dtype=torch.int64)), len(segs))
+            self.ops.synchronize()  # (the other lanes' streams read it too)
+        return got
+
+    def _sync_options(self):
+        """ahead of a launch of a `frame_options` engine: the frame slots whose entry changed, and the scales when any changed"""
+        if not self.frame_options:
+            return
+        p = self.plan
+        want = self._want_opts
+        if want is None:
+            want = self._want_opts = [(self.option_entry(p["strength"], p["steps"], p["cn"]), float(p["cn_scale"]))] * p["batch"]
+        for f, (ent, _c) in enumerate(want):
+            if ent is not self._opt_slot_src[f]:
+                tab, nseg = self._opt_seg_table(ent.layout, self.fo_layout)
+                self.ops.prompt_install(ent.buf, self.fo_buf, tab, nseg, f)
+                self._opt_slot_src[f] = ent
+        if self.fo_scale is not None:
+            nres = self._nres()
+            scales = [tuple(controlnet_scales(nres, c).tolist()) for _e, c in want]
+            if scales != self._fo_scale_last:
+                host = self._fo_scale_host
+                host.zero_()
+                host[:, :nres] = torch.tensor(scales, dtype=torch.float32)
+                self.ops.upload(self.fo_scale, host)  # (the lane's previous launch has been collected: nothing in flight reads the mirror)
+                self._fo_scale_last = scales
+
     def set_added_cond(self, pooled: torch.Tensor, time_ids):
         """SDXL micro-conditioning: pooled text embedding [add_pooled_dim] and the 6 time ids
         (orig_h, orig_w, crop_top, crop_left, target_h, target_w).  Takes effect at the next `prepare`."""
@@ -715,7 +875,13 @@ class Engine:
         t1 = a.alloc(rows, cin)
         self._gn(r, x, x2, c0, c1, hw, cfg.groups, 1e-5, rw.n1[0], rw.n1[1], True, t1)
         h = a.alloc(rows, rw.cout)
-        tv = (self._temb(net) if temb is None else temb)[step, rw.temb_off:rw.temb_off + rw.cout]
+        fo = self.frame_options  # conv1 without the time vector; norm2 adds the FRAME's slice of the time table to its input instead
+        if fo:
+            tab = self.fo_layout.view(self.fo_buf, "cn" if net is self.cn else "unet")  # frame 0's table: frame b's lies ld_tv halfs further
+            tv, ld_tv = tab[step, rw.temb_off:rw.temb_off + rw.cout], tab.numel()
+        else:
+            tv = (self._temb(net) if temb is None else temb)[step, rw.temb_off:rw.temb_off + rw.cout]
+        c1kw = {} if fo else dict(rowvec=tv)
         sc = x
         # The shortcut conv (ResnetBlock2D.conv_shortcut: 16 per denoising step with the ControlNet) depends on the block's INPUT only:
         # it shares conv1's grid (vsd_conv_gemm_group, every member at the split it has as a launch of its own: same bits) instead of
@@ -724,12 +890,15 @@ class Engine:
                    cin % 64 == 0 and c0 % 64 == 0 and c1 % 64 == 0 and rw.cout % 64 == 0 and (geom.hi, geom.wi) == (geom.hs, geom.ws))
         if grouped:
             sc = a.alloc(rows, rw.cout)
-            r.conv_group([((t1, None, geom, rw.conv1, h), dict(rowvec=tv)),
+            r.conv_group([((t1, None, geom, rw.conv1, h), c1kw),
                           ((x, x2, Geom.linear(rows), rw.shortcut, sc), dict(c0=c0, c1=c1))], split="own")
         else:
-            r.conv(t1, None, geom, rw.conv1, h, rowvec=tv)
+            r.conv(t1, None, geom, rw.conv1, h, **c1kw)
         t2 = a.alloc(rows, rw.cout)
-        self._gn(r, h, None, rw.cout, 0, hw, cfg.groups, 1e-5, rw.n2[0], rw.n2[1], True, t2)
+        if fo:
+            r.groupnorm_addvec(h, tv, ld_tv, rw.cout, hw, cfg.groups, 1e-5, rw.n2[0], rw.n2[1], True, t2, batch=self.batch)
+        else:
+            self._gn(r, h, None, rw.cout, 0, hw, cfg.groups, 1e-5, rw.n2[0], rw.n2[1], True, t2)
         if rw.shortcut is not None and not grouped:
             sc = a.alloc(rows, rw.cout)
             r.conv(x, x2, Geom.linear(rows), rw.shortcut, sc, c0=c0, c1=c1)
@@ -979,6 +1148,8 @@ class Engine:
         `down_block_additional_residuals` / `mid_block_additional_residual` adds of UNet2DConditionModel)."""
         a, net = self.arena, self.cn
         nres = len(cn_skips) + 1
+        if self.frame_options:
+            return self._controlnet_merge_frames(r, cn_mid, cn_skips, u_mid, u_skips, sizes)
         sc = self._cn_scale_consts  # fp32 [nres] in device memory: logspace(-1, 0, nres) * controlnet_scale
         assert sc.numel() >= nres
         # Only the mid-block merge is on the critical path; the decoder consumes the skips deepest first, one per ResnetBlock.
@@ -1034,6 +1205,46 @@ class Engine:
         r.conv(cn_mid, None, Geom.linear(rows), net.zero_mid, mid, out_scale_dev=sc[nres - 1:nres], residual=u_mid)
         return mid, merged
 
+    def _controlnet_merge_frames(self, r, cn_mid, cn_skips, u_mid, u_skips, sizes):
+        """`frame_options`: the scale depends on the IMAGE, which an M tile of the zero-conv's GEMM does not know.  The zero-convs are
+        recorded with out_scale = 1 and no residual (in the same grouped launches), and ONE `cn_merge_frames` launch then writes
+        out = u + scale[image][i] * z for all 13 of them (include/vsd.h)."""
+        a, net, B = self.arena, self.cn, self.batch
+        nres = len(cn_skips) + 1
+        assert nres <= L.MERGE_SEG_MAX and nres <= self.fo_scale.shape[1]
+        hh, ww = sizes[-1]
+        todo = [(cn_mid, u_mid, net.zero_mid, net.cfg.block_out_channels[-1], B * hh * ww, nres - 1, None)]
+        for i in reversed(range(len(cn_skips))):
+            (s, c, lvl), (us, uc, ulvl) = cn_skips[i], u_skips[i]
+            assert (c, lvl) == (uc, ulvl)
+            hh, ww = sizes[lvl]
+            todo.append((s, us, net.zero_convs[i], c, B * hh * ww, i, lvl))
+        calls, segs, keep = [], [], []
+        mid, merged = None, [None] * len(cn_skips)
+        for src, u, zc, c, rows, col, lvl in todo:
+            if c % 8:
+                raise ValueError(f"frame_options: a {c}-wide ControlNet residual: rows must be whole 16-byte chunks (C a multiple of 8)")
+            z, o = a.alloc(rows, c), a.alloc(rows, c)
+            calls.append(((src, None, Geom.linear(rows), zc, z), {}))
+            segs.append((z.data_ptr(), u.data_ptr(), o.data_ptr(), rows // B, c, col))
+            keep.append((z, u, o))
+            if lvl is None:
+                mid = o
+            else:
+                merged[col] = (o, c, lvl, None)
+        groupable = all(c % 64 == 0 for (_s, _u, _z, c, _r, _c, _l) in todo)
+        if self.group_merges and groupable and hasattr(self.ops, "conv_group"):
+            gmax = 7
+            for g0 in range(0, len(calls), gmax):
+                r.conv_group(calls[g0:g0 + gmax])
+        else:
+            for aa, kk in calls:
+                r.conv(*aa, **kk)
+        tab = self.ops.to_device(torch.tensor(segs, dtype=torch.int64))
+        self._merge_tabs.append(tab)
+        r.cn_merge_frames(tab, len(segs), self.fo_scale, self.fo_scale.shape[1], B, tensors=keep)
+        return mid, merged
+
     @staticmethod
     def _zip_pairs(r, first, second):
         """two recorded call lists of one topology -> pairs; calls without a twin (another op, or one list longer) go out alone"""
@@ -1043,7 +1254,7 @@ class Engine:
         for i in range(max(len(first), len(second))):
             a = first[i] if i < len(first) else None
             b = second[i] if i < len(second) else None
-            if a is not None and b is not None and a[0].__name__ == b[0].__name__ and a[0].__name__ in ("conv", "groupnorm", "attention", "tail_a", "tail_b"):
+            if a is not None and b is not None and a[0].__name__ == b[0].__name__ and a[0].__name__ in ("conv", "groupnorm", "groupnorm_addvec", "attention", "tail_a", "tail_b"):
                 r.pair(a, b)
             else:
                 for c in (a, b):
@@ -1174,7 +1385,7 @@ class Engine:
 
     def prepare(self, H: int, W: int, steps: int, strength: float, controlnet_scale: float = 1.0,
                 use_controlnet: bool = True, use_graph: Optional[bool] = None, autotune: bool = True, batch: int = 1,
-                ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False):
+                ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False, frame_options: bool = False):
         """Fix the frame geometry and schedule; build the static program and capture it into a hipGraph
         (the reference's intent at videopipeline.py:35-47, `compile_model`).
 
@@ -1196,7 +1407,21 @@ class Engine:
         frame_prompts: every frame of the launch has a prompt of its own (`use_prompts`): the program reads K / V^T from a per-frame block
         (FramePromptLayout) and records every cross-attention in the explicit form -- q GEMM over all B*hw rows, attention with image b on
         its own key rows / V^T columns, out GEMM -- at all widths (no absorbed weights: they would be per frame).  A cached prompt enters
-        a frame slot by one `prompt_install` launch ahead of the program.  Default: one prompt per launch, as before."""
+        a frame slot by one `prompt_install` launch ahead of the program.  Default: one prompt per launch, as before.
+
+        frame_options: every frame of the launch has a `strength` and a `controlnet_scale` of its own (`use_options`; `strength` and
+        `controlnet_scale` here are what a launch runs with until then).  The program reads the scheduler coefficients, the time tables and
+        the ControlNet scales from blocks of THIS engine with one slot per frame (OptionLayout; not shared with the plan's other engines):
+        the scheduler ops are the `_frames` forms, conv1 of every ResnetBlock is recorded without its time vector and norm2 adds the
+        frame's slice of the time table to its input (`groupnorm_addvec`), the zero-convs are recorded without scale and residual and one
+        `cn_merge_frames` launch per step merges all 13 residuals with the frame's scales.  Composes with device_seed and frame_prompts;
+        not with ref_mode or an SDXL UNet.  Default: one set of options per plan (`update_options`), as before."""
+        if frame_options:
+            missing = [f for f in FRAME_OPTION_OPS if not hasattr(self.ops, f)]
+            if missing:
+                raise ValueError(f"frame_options=True needs the op(s) {', '.join(missing)}, which this ops object does not have")
+            if ref_mode or self.unet.add_l1 is not None:
+                raise ValueError("frame_options=True: reference-only and SDXL programs keep one set of options per plan (update_options)")
         if frame_prompts and not hasattr(self.ops, "prompt_install"):
             raise ValueError("frame_prompts=True needs the op prompt_install, which this ops object does not have")
         if device_seed and not all(hasattr(self.ops, f) for f in ("add_noise_seeded", "lcm_step_seeded")):
@@ -1230,6 +1455,7 @@ class Engine:
             self.pblock = PromptBlock(self.ops, src.layout)
             self._installed = None
         self.frame_prompts = bool(frame_prompts)
+        self.frame_options = bool(frame_options)
         if use_controlnet and self.cn is None:
             raise RuntimeError("no ControlNet weights loaded")
         if ref_mode and (batch != 1 or use_controlnet or (H // 8) * (W // 8) % 8):
@@ -1261,7 +1487,20 @@ class Engine:
         # the scheduler coefficients of step i, then the 13 ControlNet residual scales; plus the time-embedding projections
         # of every step.  `update_options` rewrites them in place -- a new strength / controlnet_scale needs no re-capture.
         ncn = 16
-        if self.is_slot:  # computed by the parent engine's prepare / update_options
+        self.fo_layout = self.fo_buf = self.fo_scale = self._fo_scale_host = self._fo_scale_last = None
+        self._want_opts, self._opt_slot_src, self._merge_tabs = None, [None] * B, []
+        if frame_options:
+            # this engine's OWN blocks, one slot per frame: the program records frame 0's addresses and the strides; `_sync_options` fills
+            # the slots ahead of every launch (here, before the warm-up run, with the options `prepare` was given)
+            self.fo_layout = OptionLayout(n, self._option_cols(use_controlnet), B)
+            self.fo_buf = ops.zeros(self.fo_layout.nbytes, dtype=torch.uint8)
+            c = self.fo_layout.view(self.fo_buf, "coef")
+            if use_controlnet:
+                assert self._nres() <= ncn
+                self.fo_scale = ops.zeros(B, ncn, dtype=torch.float32)
+                self._fo_scale_host = torch.zeros(B, ncn, dtype=torch.float32, pin_memory=torch.cuda.is_available())
+            self.shared["n"] = n
+        elif self.is_slot:  # computed by the parent engine's prepare / update_options
             c = self.shared.get("consts")
             assert c is not None and self.shared.get("n") == n, "prepare the parent engine with the same schedule first"
         else:
@@ -1275,13 +1514,14 @@ class Engine:
                     temb[name] = ops.zeros(n, net.temb_proj.n)
             self.shared["ref_mode"] = bool(ref_mode)
             self._write_constants(sched, controlnet_scale, use_controlnet)
-        self._cn_scale_consts = c[2 + 6 * n:]
+        self._cn_scale_consts = None if frame_options else c[2 + 6 * n:]
         # noise draws: the reference resets the global CPU generator to a fresh-Generator state on every
         # frame (videopipeline.py:126), so for a fixed shape the draws are the same every frame.
         # Where the noise comes from is chosen here, once: add_noise(r, x0, kind, draw, coef, batch, out) and lcm_step(r, eps, cur, draw,
         # coef, batch, nxt, den, dec_in) record the scheduler ops of either source (include/vsd.h: kind 0 draw d = noise[d], kind 1 draw
         # d = noise_ref[d]; a step with draw 0 adds none).
         ref_draws = None
+        cstride = self.fo_layout.coef_stride if frame_options else 0  # floats between two frames' coefficients
         if device_seed:
             # one seed per frame of the launch, u32 (low, high) pairs = little-endian u64: this engine's own (a slot has its own)
             self.noise = self.noise_ref = None
@@ -1289,9 +1529,13 @@ class Engine:
             self._seed_host = torch.zeros(B, dtype=torch.int64, pin_memory=torch.cuda.is_available())
 
             def add_noise(r, x0, kind, draw, coef, batch, out):
+                if frame_options:
+                    return r.add_noise_frames(x0, None, seeds, kind, draw, coef, cstride, hw0, batch, out)
                 r.add_noise_seeded(x0, seeds, kind, draw, coef, hw0, batch, out)
 
             def lcm_step(r, eps, cur, draw, coef, batch, nxt, den, dec_in):
+                if frame_options:  # (draw 0: the step adds no noise -- neither source)
+                    return r.lcm_step_frames(eps, cur, None, seeds if draw else None, 0, draw, coef, cstride, hw0, batch, nxt, den, dec_in)
                 r.lcm_step_seeded(eps, cur, seeds, 0, draw, coef, hw0, batch, nxt, den, dec_in)
         else:
             self.seed_dev = self._seed_host = None
@@ -1299,9 +1543,13 @@ class Engine:
             self.noise = ops.to_device(draws)
 
             def add_noise(r, x0, kind, draw, coef, batch, out):
+                if frame_options:
+                    return r.add_noise_frames(x0, self.noise[draw], None, 0, 0, coef, cstride, hw0, batch, out)
                 r.add_noise_dev(x0, (self.noise_ref if kind else self.noise)[draw], coef, hw0, batch, out)
 
             def lcm_step(r, eps, cur, draw, coef, batch, nxt, den, dec_in):
+                if frame_options:
+                    return r.lcm_step_frames(eps, cur, self.noise[draw] if draw else None, None, 0, 0, coef, cstride, hw0, batch, nxt, den, dec_in)
                 r.lcm_step_dev(eps, cur, self.noise[draw] if draw else None, coef, hw0, batch, nxt, den, dec_in)
         a = self.arena
         enc_in = a.alloc(B * H * W, 8)
@@ -1400,11 +1648,12 @@ class Engine:
         self.program = r.flavor(0 if self.overlap_controlnet or not self._twin_now else 1)
         self.program_serial = r.flavor(1) if self._twin_now and self.overlap_controlnet and use_controlnet else self.program
         self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=n, batch=B,
-                         ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), tuned_for_lanes=bool(self.tune_for_lanes),
+                         ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), frame_options=bool(frame_options), tuned_for_lanes=bool(self.tune_for_lanes),
                          sizes=sizes, timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=a.peak)
         # per-shape kernel configuration (timed once per shape, cached in ops.tile_override), warm-up, capture
         torch.cuda.synchronize() if torch.cuda.is_available() else None  # allocation fills vs. kernel streams
         self._sync_prompt()
+        self._sync_options()
         if autotune:  # (only shapes missing from the shared table are timed: a slot with the parent's batch size finds all)
             self.autotune()
         self.program.run()
@@ -1486,6 +1735,9 @@ class Engine:
                 elif op == "groupnorm":
                     count("pair_groupnorm")
                     count("pair_gn_second", gn_launches(aa, ka) - 1)
+                elif op == "groupnorm_addvec":  # (src, addvec, ld, c, hw, groups, ...)
+                    count("pair_groupnorm_addvec")
+                    count("pair_gn_second", gn_launches((None, None, aa[3], 0, aa[4], aa[5]), ka) - 1)
                 else:
                     count("pair_" + op)
                 continue
@@ -1508,6 +1760,8 @@ class Engine:
                 count("splitk_reduce", conv_reducer(a, k))
             elif name == "groupnorm":
                 count("gn_second", gn_launches(a, k) - 1)
+            elif name == "groupnorm_addvec":
+                count("gn_second", gn_launches((None, None, a[3], 0, a[4], a[5]), k) - 1)
         return sum(v for k, v in kinds.items() if k != "convs_in_groups"), kinds
 
     def _capture(self, r: Recorder, serial: bool = False):
@@ -1599,6 +1853,8 @@ class Engine:
         follow (they share the constant block)."""
         if self.plan is None or self.is_slot:
             raise RuntimeError("update_options: prepare the parent engine first")
+        if self.plan.get("frame_options"):
+            raise RuntimeError("update_options: a frame_options plan takes its options per launch (use_options)")
         sched = LCMSchedule(strength, self.plan["steps"])
         if len(sched) != self.plan["n"]:
             return False
@@ -1639,6 +1895,7 @@ class Engine:
         lane's side stream (default: `self.overlap_launch`); pass False when a launch of the lane that OWNS that stream
         (lane + 2 mod 4) may be in flight -- two busy queues on one command-processor pipe take turns (ops.HipOps)."""
         self._sync_prompt()
+        self._sync_options()
         if self.graph is not None:
             ov = self.overlap_launch if overlap is None else overlap
             self.ops.seq_launch(self.graph if ov else self.graph_serial)

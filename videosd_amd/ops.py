@@ -1016,6 +1016,34 @@ class HipOps:
         self.__dict__.setdefault("_seg_tables", {})[segs_dev.data_ptr()] = segs_dev
         self.ctx.call("vsd_prompt_install", self._p(src_buf), self._p(dst_buf), self._p(segs_dev), int(nseg), int(frame), self.raw_stream(0))
 
+    # ---- per-frame options (include/vsd.h: strength and ControlNet scale per frame of one launch)
+    def add_noise_frames(self, x0, noise_f32, seeds_dev, kind, draw, coef_dev, coef_stride, hw, batch, out):
+        """`add_noise_dev` (noise_f32) or `add_noise_seeded` (seeds_dev, kind, draw) -- exactly one of the two -- with image b reading its two
+        coefficients at coef_dev + b * coef_stride floats"""
+        self.ctx.call("vsd_add_noise_frames", self._p(x0), self._p(noise_f32), self._p(seeds_dev), int(kind), int(draw), self._p(coef_dev),
+                      int(coef_stride), hw, batch, self._p(out), self.s)
+
+    def lcm_step_frames(self, eps, sample, noise_f32, seeds_dev, kind, draw, coef_dev, coef_stride, hw, batch, prev, denoised, dec_in=None):
+        """`lcm_step_dev` / `lcm_step_seeded` with image b reading its six coefficients at coef_dev + b * coef_stride floats; neither noise
+        source: the step adds no noise"""
+        self.ctx.call("vsd_lcm_step_frames", self._p(eps), self._p(sample), self._p(noise_f32), self._p(seeds_dev), int(kind), int(draw),
+                      self._p(coef_dev), int(coef_stride), hw, batch, self._p(prev), self._p(denoised), self._p(dec_in), self.s)
+
+    def groupnorm_addvec(self, src, addvec, ld_addvec, c, hw, groups, eps, gamma, beta, silu, out, batch=1):
+        """`groupnorm` of fp32(src) + fp32(addvec of the image): addvec fp16, image b's vector at addvec + b * ld_addvec halfs"""
+        ws = self.workspace("gn", max(1, batch) * int(self.ctx.lib.vsd_groupnorm_workspace_bytes(hw, c, groups)))
+        self.ctx.call("vsd_groupnorm_addvec", self._p(src), self._p(addvec), int(ld_addvec), c, hw, max(1, batch), groups, eps, self._p(gamma),
+                      self._p(beta), int(silu), self._p(out), self._p(ws), self.s)
+
+    def cn_merge_frames(self, segs_dev, nseg: int, scales_dev, scale_stride: int, batch: int, tensors=None):
+        """out = u + scale[image][col] * z for every segment of the table, one launch.  segs_dev: int64 [nseg][6] in device memory =
+        (z address, u address, out address, rows per image, channels, scale column) per segment; scales_dev: fp32 [batch][scale_stride].
+        tensors: the (z, u, out) tensors the table names, where the caller has them (the op emulator of the tests works on those; unused
+        here).  The library checks a table when it first sees it -- one blocking copy, so never first inside a capture -- and remembers it
+        by address: the table is kept alive here."""
+        self.__dict__.setdefault("_merge_tables", {})[segs_dev.data_ptr()] = segs_dev
+        self.ctx.call("vsd_cn_merge_frames", self._p(segs_dev), int(nseg), self._p(scales_dev), int(scale_stride), int(batch), self.s)
+
     def adain(self, x, stats, stats_ref, rows, c, out, eps=1e-6):
         """reference-only AdaIN: per-channel re-normalisation of x to the banked statistics (fp32 [c][2] sum / sumsq)"""
         self.ctx.call("vsd_adain", self._p(x), self._p(stats), self._p(stats_ref), rows, c, eps, self._p(out), self.s)

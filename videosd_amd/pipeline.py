@@ -52,6 +52,7 @@ def load_or_synthesize(spec, prefix: str, filename: str, device, snapshot_file: 
         return w, path
     return W.synthesize(spec, prefix, device=device), "synthetic"
 
+_FRAME_OPTIONS = ("frame_options", True)  # ... and in THAT mode (the last element when on)
 _FRAME_PROMPTS = ("frame_prompts", True)  # ... and in THAT mode (after _DEVICE_SEED when both are on)
 _DEVICE_SEED = ("device_seed", True)  # the element a plan key ends with in that mode (no prompt key of an SDXL plan looks like it)
 
@@ -86,6 +87,13 @@ class VideoSDPipeline:
         self.frame_prompts = bool(kwargs.get("frame_prompts", False))
         if self.frame_prompts:
             self.per_frame_prompt = True
+        # extension, off by default: every frame of a launch has a `strength` and a `controlnet_scale` of its own -- `infer_batch` /
+        # `submit_batch` take either as a number or as a sequence of one per frame, and a worker coalesces frames of sessions whose
+        # sliders stand differently (`per_frame_options` / `option_class`, read by dispatch.py).  The program then reads the scheduler
+        # coefficients, time tables and ControlNet scales per frame (Engine.prepare(frame_options=True)); a changed option rewrites a frame
+        # slot ahead of the launch, so nothing is drained.  Off: one (strength, controlnet_scale) per plan (`Engine.update_options`).
+        # SDXL and reference-only programs keep the default form either way.
+        self.frame_options = bool(kwargs.get("frame_options", False))
         # launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on
         # launch stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch
         self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
@@ -94,6 +102,10 @@ class VideoSDPipeline:
         except KeyError:
             print("Model name and controlnet model must be specified")  # videopipeline.py:24-26
             raise
+        if self.frame_options and self.is_xl:
+            self.frame_options = False
+        if self.frame_options:
+            self.per_frame_options = True
         # Per-session state without stalls (server.py:90-93: options live on each VideoSDTrack; :132-137: every session's
         # frames go through the same actors).  Two LRU caches:
         #   prompts: prompt key -> PromptBlock (cross-attention K / V^T + absorbed weights of every layer, ~40 MB, built on the
@@ -306,6 +318,23 @@ class VideoSDPipeline:
         self._ref_img = img
         self._ref_epoch += 1
 
+    def option_class(self, options) -> int:
+        """What two requests must share to run in ONE launch of a `frame_options` pipeline although their `strength` / `controlnet_scale`
+        differ: the NUMBER of timesteps of (strength, steps) -- the program's length (`options`: the kwargs of an `infer` call)."""
+        from .lcm import lcm_timesteps
+
+        return len(lcm_timesteps(float(options.get("strength", 0.4)), int(options.get("steps", 20))))
+
+    @staticmethod
+    def _per_frame(value, n: int, name: str):
+        """`strength` / `controlnet_scale` of a launch of n frames -> n floats: a number for every frame, or a sequence of one per frame"""
+        if isinstance(value, (int, float, np.integer, np.floating)):
+            return [float(value)] * n
+        vals = [float(v) for v in value]
+        if len(vals) != n:
+            raise ValueError(f"{name} must be a number or a sequence of one per frame: {len(vals)} value(s) for {n} frame(s)")
+        return vals
+
     def can_batch(self, **options) -> bool:
         """May the worker coalesce queued frames with these options into one launch?  (reference-only frames go alone)"""
         return not (self.honor_ref_flag and options.get("ref", False))
@@ -382,7 +411,9 @@ class VideoSDPipeline:
         weights for all of them.  Extension of the reference surface; `RemotePipeline(batch=B)` coalesces queued
         `infer` calls into this.
         prompts (objects built with `frame_prompts=True`): one prompt per frame, each what `prompt` accepts; frame i is then what `infer`
-        gives it with prompts[i].  None: `prompt` for every frame."""
+        gives it with prompts[i].  None: `prompt` for every frame.
+        strength / controlnet_scale (objects built with `frame_options=True`): a number, or a sequence of one per frame; all strengths of a
+        launch must give the same number of timesteps."""
         extra = {} if prompts is None else {"prompts": prompts}
         return self.collect_batch(self.submit_batch(imgs, prompt=prompt, height=height, width=width, strength=strength,
                                                     steps=steps, guidance_scale=guidance_scale, ref=ref,
@@ -471,9 +502,21 @@ class VideoSDPipeline:
         # slider drag in the client (server.py:163-197) does not rebuild or re-capture anything.
         from .lcm import lcm_timesteps
 
-        n_eff = len(lcm_timesteps(float(strength), int(steps)))  # ValueError for an empty schedule: the caller's problem
+        # per-frame options: one (strength, controlnet_scale) per frame; the launch's program is fixed by their COMMON number of timesteps
+        strengths = self._per_frame(strength, len(imgs), "strength")
+        cn_scales = self._per_frame(controlnet_scale, len(imgs), "controlnet_scale")
+        frame_opts = bool(getattr(self, "frame_options", False)) and not self.is_xl and not use_ref
+        if not frame_opts and (len(set(strengths)) > 1 or len(set(cn_scales)) > 1):
+            raise ValueError("strength / controlnet_scale with different values per frame need a pipeline built with frame_options=True "
+                             "(and neither an SDXL nor a reference-only program): this launch runs one pair of options")
+        counts = [len(lcm_timesteps(v, int(steps))) for v in dict.fromkeys(strengths)]  # ValueError for an empty schedule: the caller's problem
+        if len(set(counts)) > 1:
+            raise ValueError(f"the strengths {strengths} give different numbers of timesteps at steps={int(steps)} ({sorted(set(counts))}): "
+                             "the frames of one launch run one program; launch them separately")
+        strength, controlnet_scale = strengths[0], cn_scales[0]
+        n_eff = counts[0]
         # (SDXL: the pooled text embedding is baked into the time embeddings at `prepare`, so the prompt is part of the program)
-        plan_key = (height, width, int(steps), n_eff, use_cn, use_ref) + ((pkey,) if self.is_xl else ()) + ((_DEVICE_SEED,) if getattr(self, "device_seed", False) else ()) + ((_FRAME_PROMPTS,) if plist is not None else ())
+        plan_key = (height, width, int(steps), n_eff, use_cn, use_ref) + ((pkey,) if self.is_xl else ()) + ((_DEVICE_SEED,) if getattr(self, "device_seed", False) else ()) + ((_FRAME_PROMPTS,) if plist is not None else ()) + ((_FRAME_OPTIONS,) if frame_opts else ())
         seeds = None
         if getattr(self, "device_seed", False):
             seeds = [seed] * len(imgs) if isinstance(seed, (int, np.integer)) else list(seed)
@@ -484,6 +527,8 @@ class VideoSDPipeline:
         eng = self._engine_for(plan_key, opts, len(imgs), lane, prompt=pblock, prompt_text=prompt)
         # this lane's launch reads ITS copy of the constants: the other lanes may run other prompts
         eng.use_prompts(pblock) if plist is not None else eng.use_prompt(pblock)
+        if frame_opts:  # (a changed frame slot is rewritten on this lane's stream ahead of the program: nobody waits)
+            eng.use_options(list(zip(strengths, cn_scales)))
         if use_ref and getattr(eng, "_ref_epoch", None) != self._ref_epoch:
             rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), width, height), dtype=np.uint8)
             eng.ops.upload(eng.ref_u8, torch.from_numpy(np.array(rf, copy=True)))  # (PIL's buffer is read-only)
@@ -505,6 +550,9 @@ class VideoSDPipeline:
         self._outstanding.append(eng)
         self._lanes_busy.append(int(lane))
         self._note("upload_enqueue", t0)
+        if frame_opts:  # (the handle keeps the launch's prompt and option entries alive: their installs may not have executed yet)
+            return (eng, len(imgs), yuv if any(yuv) else None, i420 is not None, tuple(pblock) if plist is not None else (),
+                    tuple(e for e, _c in eng._want_opts))
         if plist is not None:  # (the handle keeps the launch's cache entries alive: their installs may not have executed yet)
             return (eng, len(imgs), yuv if any(yuv) else None, i420 is not None, tuple(pblock))
         if any(yuv):  # (which results go back as I420, and whether the device converts them)
@@ -609,6 +657,8 @@ class VideoSDPipeline:
                 pk += (_DEVICE_SEED,)
             if getattr(self, "frame_prompts", False):
                 pk += (_FRAME_PROMPTS,)
+            if getattr(self, "frame_options", False) and not self.is_xl:
+                return False  # (options are per frame slot of the lane's own engine: a new value never waits for another lane)
             plan = self._plans.get(pk)
             if plan is None:
                 return False
@@ -623,10 +673,11 @@ class VideoSDPipeline:
         change rewrites that program's device constants, nothing else."""
         height, width, steps, _n, use_cn, use_ref = plan_key[:6]
         strength, cn_scale = opts
+        frame_opts = _FRAME_OPTIONS in plan_key[6:]  # (options per frame slot of each engine: the plan has none, `opts` only seeds `prepare`)
         plan = self._plans.get(plan_key)
         if plan is not None:
             self._plans.move_to_end(plan_key)
-            if opts != plan["opts"]:
+            if not frame_opts and opts != plan["opts"]:
                 if self._plan_busy(plan):
                     raise RuntimeError("cannot change strength / controlnet_scale of a plan with launches in flight: collect them first")
                 t0 = time.perf_counter()
@@ -650,7 +701,7 @@ class VideoSDPipeline:
                     for e in self._plans.pop(pk)["engines"].values():
                         e._destroy_graphs()
             eng = self.model.make_slot(share_plan=False, lane=lane)  # its own schedule constants: the other programs keep running
-            plan = self._plans[plan_key] = {"root": eng, "opts": opts, "engines": {}}
+            plan = self._plans[plan_key] = {"root": eng, "opts": None if frame_opts else opts, "engines": {}}
         else:
             eng = plan["root"].make_slot(lane=lane)
         if prompt is not None:
@@ -666,6 +717,8 @@ class VideoSDPipeline:
         mode = {"device_seed": True} if _DEVICE_SEED in plan_key[6:] else {}
         if _FRAME_PROMPTS in plan_key[6:]:
             mode["frame_prompts"] = True
+        if frame_opts:
+            mode["frame_options"] = True
         eng.prepare(height, width, steps, strength, controlnet_scale=cn_scale, use_controlnet=use_cn, batch=batch, ref_mode=use_ref,
                     autotune=self.tuning_mode != "table", **mode)
         eng._ref_epoch = None
@@ -729,6 +782,10 @@ class VideoSDPipeline:
         if getattr(self, "frame_prompts", False):
             raise ValueError("export_plan: this pipeline was built with frame_prompts=True; a plan file holds ONE prompt's constants and the C "
                              "library has no per-frame prompt entry point yet: export from a pipeline built without it")
+        if getattr(self, "frame_options", False):
+            raise ValueError("export_plan: this pipeline was built with frame_options=True; its programs call vsd_add_noise_frames, "
+                             "vsd_lcm_step_frames, vsd_groupnorm_addvec and vsd_cn_merge_frames, which are not plan functions: export from a "
+                             "pipeline built without it (a loaded plan follows the sliders through vsd_plan_set_options)")
         self._require_idle("export a plan")
         w, h = int(options.get("width", 640)), int(options.get("height", 360))
         imgs = [Image.new("RGB", (w, h), (127, 127, 127)) for _ in range(int(frames_per_launch))]

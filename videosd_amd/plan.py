@@ -230,6 +230,10 @@ def export_plan(engine, path: str) -> dict:
     if engine.plan.get("frame_prompts"):
         raise ValueError("export_plan: this engine was prepared with frame_prompts=True; a plan file holds ONE prompt's constants (per-frame "
                          "prompts have no C entry point yet): export the plan of an engine prepared without it")
+    if engine.plan.get("frame_options"):
+        raise ValueError("export_plan: this engine was prepared with frame_options=True; its program calls vsd_add_noise_frames, vsd_lcm_step_frames, "
+                         "vsd_groupnorm_addvec and vsd_cn_merge_frames, which are not plan functions: export the plan of an engine prepared "
+                         "without it (a loaded plan follows strength / ControlNet scale through vsd_plan_set_options)")
     ops.synchronize()
     calls = []
 
