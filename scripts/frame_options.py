@@ -116,7 +116,7 @@ def device_costs():
         f"host {', '.join(f'{a:.2f}' for a, _b in ms)} ms (median {np.median([a for a, _b in ms]):.2f}); between events on the stream "
         f"{', '.join(f'{b:.2f}' for _a, b in ms)} ms (median {np.median([b for _a, b in ms]):.2f})")
     # one slot install
-    tab, nseg = eng._opt_seg_table(ent.layout, eng.fo_layout)
+    tab, nseg = eng._seg_table(ent.layout, eng.fo_layout)
     nbytes = sum(int(r) * int(rb) for _so, _do, r, rb, _p, _f in tab.cpu().tolist())
     us = []
     for _ in range(5):

@@ -66,7 +66,7 @@ for i in range(40):
     t1 = time.perf_counter()
     eng.infer_u8(frames[i % 12])
     lat.append((time.perf_counter() - t1) * 1e3)
-    gpu.append(getattr(eng, "last_gpu_ms", 0.0))
+    gpu.append(eng.last_gpu_ms or 0.0)
 out = {"tag": tag, "controlnet": use_cn, "retune": retune, "table_entries_loaded": n_loaded, "prepare_s": round(prepare_s, 2),
        "p50_ms": round(statistics.median(lat), 3), "min_ms": round(min(lat), 3), "gpu_p50_ms": round(statistics.median(gpu), 3),
        "n_ops": plan["n_ops"], "launches": launches, "launches_by_kind": kinds, "launches_one_stream_form": launches_serial,

@@ -169,6 +169,105 @@ def test_a_slot_owns_its_staging_buffers_and_events(mini):
     assert not np.array_equal(slot.collect_u8(), out_a)
 
 
+def test_a_slot_owns_its_i420_buffers(mini):
+    """... nor the device and pinned buffers of the I420 output: a slot made after the parent's first `collect_i420` used to inherit them,
+    and two lanes then wrote their planes into one buffer.  (An op emulator with a trivial `rgb_to_i420`: the planes are the channels.)"""
+
+    class I420Ops(FakeOps):
+        def clone(self, lane=None):
+            return I420Ops()
+
+        def rgb_to_i420(self, src, h, w, y, u, v):
+            y.copy_(src[..., 0].reshape(-1))
+            u.copy_(src[::2, ::2, 1].reshape(-1))
+            v.copy_(src[::2, ::2, 2].reshape(-1))
+
+    def planes(e):
+        rgb = e.out_u8.numpy()
+        return rgb[..., 0], rgb[::2, ::2, 1], rgb[::2, ::2, 2]
+
+    wu, wc, wv, text = mini
+    eng = Engine(I420Ops(), C.MINI_UNET, C.MINI_CONTROLNET, C.TAESD, wu, wc, wv)
+    eng.set_text_embeds(text)
+    eng.prepare(64, 64, 2, 0.6, use_controlnet=True, use_graph=False)
+    a, b = _frame(64, 64, seed=1), _frame(64, 64, seed=2)
+    eng.submit_u8(a)
+    first = eng.collect_i420()                   # the parent's I420 buffers exist now
+    slot = eng.make_slot()
+    slot.prepare(64, 64, 2, 0.6, use_controlnet=True, use_graph=False)
+    eng.submit_u8(a)
+    slot.submit_u8(b)
+    got_a, got_b = eng.collect_i420(), slot.collect_i420()
+    for got, e in ((got_a, eng), (got_b, slot)):
+        y, u, v = planes(e)
+        assert np.array_equal(got.y, y) and np.array_equal(got.u, u) and np.array_equal(got.v, v)
+    assert got_a == first and got_a != got_b
+    assert slot._i420_stage[0] is not eng._i420_stage[0] and slot._i420_stage[1] is not eng._i420_stage[1]
+
+
+def test_every_attribute_of_an_engine_is_declared_and_a_slot_starts_empty(mini):
+    """An engine's attributes are the ones `__init__` leaves: a full life -- every mode of `prepare`, prompts and options per frame, the
+    submits and collects, `update_options`, `make_slot` -- adds none.  And a fresh slot holds nothing of its parent's own state: every
+    attribute `_reset_own_state` declares has its empty value.  (Fails when a per-engine attribute comes into being anywhere else.)"""
+    import frame_option_cases as FO
+
+    class Ops(FO.FrameOptionFakeOps):
+        """... plus stand-ins for the seeded scheduler ops (the emulator has the table noise only) and the crop box of a frame of the plan's size"""
+
+        def clone(self, lane=None):
+            return Ops()
+
+        def add_noise_seeded(self, *a, **k):
+            pass
+
+        def lcm_step_seeded(self, *a, **k):
+            pass
+
+        def add_noise_frames(self, x0, noise_f32, seeds_dev, *a, **k):
+            if seeds_dev is None:
+                super().add_noise_frames(x0, noise_f32, seeds_dev, *a, **k)
+
+        def lcm_step_frames(self, eps, sample, noise_f32, seeds_dev, *a, **k):
+            if seeds_dev is None:
+                super().lcm_step_frames(eps, sample, noise_f32, seeds_dev, *a, **k)
+
+        def center_crop_box(self, src_w, src_h, dst_w, dst_h):
+            assert (src_w, src_h) == (dst_w, dst_h)
+            return 0, 0, src_w, src_h
+
+    wu, wc, wv, text = mini
+    text2 = (torch.randn(77, C.MINI_UNET.cross_dim, generator=torch.Generator().manual_seed(8)) * 0.5).half()
+    eng = Engine(Ops(), C.MINI_UNET, C.MINI_CONTROLNET, C.TAESD, wu, wc, wv)
+    declared = set(vars(eng))
+    eng.set_text_embeds(text)
+    blocks = [eng.build_prompt(text), eng.build_prompt(text2)]
+    eng.use_prompts(blocks)
+    plan = eng.prepare(64, 64, 2, 0.6, controlnet_scale=1.5, use_graph=False, batch=2, device_seed=True, frame_prompts=True, frame_options=True)
+    assert plan["device_seed"] and plan["frame_prompts"] and plan["frame_options"]
+    eng.use_prompts(blocks[::-1])
+    eng.use_options([FO.OPT_A, FO.OPT_B])
+    frames = np.stack([_frame(64, 64, seed=1), _frame(64, 64, seed=2)])
+    eng.submit_u8(frames, seeds=[5, 6])
+    assert eng.collect_u8().shape == frames.shape
+    eng.submit_raw_u8(list(frames))
+    eng.collect_u8()
+    other = Engine(Ops(), C.MINI_UNET, C.MINI_CONTROLNET, C.TAESD, wu, wc, wv)
+    other.set_text_embeds(text)
+    other.prepare(64, 64, 2, 0.6, use_graph=False)
+    assert other.update_options(0.8, 0.3) is True
+    slot = eng.make_slot()
+    assert set(vars(eng)) == declared and set(vars(other)) == declared and set(vars(slot)) == declared
+    empty = Engine.__new__(Engine)
+    empty._reset_own_state()
+    own = vars(empty)
+    assert {"plan", "program", "program_serial", "buffers", "frame_u8", "out_u8", "pblock", "seed_dev", "fo_buf", "_stage", "_raw_stage",
+            "_i420_stage", "_i420_queued", "_vt_pool", "_merge_tabs", "last_gpu_ms"} <= set(own) < declared
+    for name, value in own.items():
+        assert type(getattr(slot, name)) is type(value) and getattr(slot, name) == value, name
+        assert value is None or getattr(slot, name) is not getattr(eng, name) or isinstance(value, (bool, int)), name
+    assert eng.program is not None and eng._stage is not None and eng._raw_stage is not None and eng.seed_dev is not None  # (the parent keeps its own)
+
+
 @pytest.mark.parametrize("H,W,steps", [(64, 64, 2), (64, 64, 1)])
 def test_reference_only_mode_matches_oracle(mini, H, W, steps):
     """SURVEY 8f-4 (lcm_reference_pipeline.py:498-794, 855-890): per step a WRITE pass over the noised reference latents

@@ -178,7 +178,7 @@ def test_only_the_changed_slots_are_installed(world):
 def test_two_slots_on_different_lanes_keep_their_own_lists(world):
     eng, p, frames, runs = world["eng"], world["p"], world["frames"], world["runs"]
     slot = eng.make_slot(lane=1)
-    assert slot.pblock is None and slot._slot_src == [] and slot._want_list is None
+    assert slot.pblock is None and slot._prompt_slots is None and slot._want_list is None
     slot.use_prompts([p[1], p[1], p[0]])
     slot.prepare(H, Wd, STEPS, 0.6, batch=B, frame_prompts=True, **PREP)
     assert slot.pblock is not eng.pblock and slot.pblock.layout is eng.pblock.layout

@@ -5,7 +5,8 @@ per frame.
 Replaces the body of LatentConsistencyModelPipeline_controlnet.__call__
 (/root/reference/diffusert/lcm/lcm_controlnet.py:379-618) and the diffusers modules it drives.  All
 compute goes through an `ops` object (videosd_amd.ops.HipOps -> libvsd.so); this module only decides
-which buffers each kernel reads and writes.
+which buffers each kernel reads and writes.  The packed weights are netweights.py, the arena / recorder / capture of the
+static program program.py, the prompt and option blocks with their layouts blocks.py; their names are importable from here.
 
 Data layout in HBM
   * activations: fp16 [H*W][C] (channels-last), bump-allocated from one arena that is rewound at every
@@ -15,483 +16,62 @@ Data layout in HBM
   * per-(strength,steps) constants: time-embedding projections of every ResnetBlock for every step, the
     noise draws, scheduler coefficients; per-prompt constants: cross-attention K and V^T of every layer.
 """
-from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+import copy
+import os
+from collections import OrderedDict
+from typing import Dict, Optional
 
 import numpy as np
 import torch
 
 from . import lib as L
+from .blocks import (FRAME_OPTION_OPS, MAX_OPTION_ENTRIES, FramePromptLayout, FrameSlots, OptionEntry, OptionLayout,  # noqa: F401
+                     PromptBlock, PromptLayout, controlnet_scales, option_segments, prompt_segments, schedule_constants)
 from .config import ControlNetConfig, TAESDConfig, UNetConfig
 from .lcm import LCMSchedule, timestep_sinusoid, w_embedding
+from .netweights import XATTN_ABSORB_MIN_C, BlockW, NetWeights, ResnetW, TAESDWeights, TransformerW  # noqa: F401
 from .ops import Geom
-from .packing import PackedConv, add_frag, pack_conv, pack_geglu_ln, pack_linear, pack_linear_cat, pack_linear_ln
-from .weights import skip_channels
+from .packing import _round_up as _ru
+from .program import SYNC_OPS, Arena, Recorder, capture, flat_calls, launches_by_kind
 
 
-def _ru(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
+def _env_switch(name: str, default: bool) -> bool:
+    """an A/B switch of the environment: unset -> `default`, "1" -> on, anything else -> off"""
+    v = os.environ.get(name)
+    return default if v is None else v == "1"
 
 
-class Arena:
-    """Bump allocator over large device chunks; `mark`/`rewind` give every denoising step the same addresses."""
+class SchedulerOps:
+    """Records a plan's scheduler ops for the noise source and the coefficient form `prepare` chose (include/vsd.h: kind 0 draw d =
+    noise[d], kind 1 draw d = noise_ref[d]; a step with draw 0 adds none).  seeds: one per frame, on the device (`device_seed`), else the
+    host draws `noise` / `noise_ref`; coef_stride: floats between two frames' coefficients (`frame_options`), 0: one set per launch."""
 
-    def __init__(self, ops, chunk_bytes: int = 256 << 20):
-        self.ops = ops
-        self.chunk_bytes = chunk_bytes
-        self.chunks: List[torch.Tensor] = []
-        self.ci = 0
-        self.off = 0
-        self.peak = 0
+    def __init__(self, hw: int, noise=None, noise_ref=None, seeds=None, coef_stride: int = 0):
+        self.hw, self.noise, self.noise_ref, self.seeds, self.coef_stride = hw, noise, noise_ref, seeds, coef_stride
 
-    def alloc(self, rows: int, cols: int, dtype=torch.float16) -> torch.Tensor:
-        esz = torch.empty(0, dtype=dtype).element_size()
-        nbytes = _ru(rows * cols * esz, 256)
-        if getattr(self.ops, "allocator", None) is not None:  # debugging hook (ops.HipOps.allocator): tensor by tensor
-            self.peak += nbytes
-            return self.ops.empty(rows, cols, dtype=dtype)
-        while True:
-            if self.ci >= len(self.chunks):  # (a tensor larger than the usual chunk gets a chunk of its own size)
-                self.chunks.append(self.ops.empty(max(self.chunk_bytes, nbytes), dtype=torch.uint8))
-                self.off = 0
-            if self.off + nbytes <= self.chunks[self.ci].numel():
-                break
-            self.ci += 1
-            self.off = 0
-        t = self.chunks[self.ci][self.off:self.off + rows * cols * esz].view(dtype).view(rows, cols)
-        self.off += nbytes
-        self.peak = max(self.peak, sum(c.numel() for c in self.chunks[:self.ci]) + self.off)
-        return t
-
-    def mark(self) -> Tuple[int, int]:
-        return (self.ci, self.off)
-
-    def rewind(self, m: Tuple[int, int]):
-        self.ci, self.off = m
-
-
-class Recorder:
-    """Records op calls as a static program; `run` replays them on the real ops object."""
-
-    def __init__(self, ops):
-        self.ops = ops
-        self.calls = []
-
-    def __getattr__(self, name):
-        fn = getattr(self.ops, name)
-
-        def rec(*a, **k):
-            self.calls.append((fn, a, k))
-
-        return rec
-
-    def run(self):
-        for fn, a, k in self.calls:
-            fn(*a, **k)
-
-    # a stretch of the program recorded in two FORMS (same buffers, same results): `flavor(i)` is the program with form i
-    def variants(self, form0, form1):
-        self.calls.append((_variants, (form0, form1), {}))
-
-    def flavor(self, i: int) -> "Recorder":
-        out = Recorder(self.ops)
-        for c in self.calls:
-            if c[0] is _variants:
-                out.calls += c[1][i]
-            else:
-                out.calls.append(c)
-        return out
-
-
-def _variants(*a, **k):
-    raise RuntimeError("a program with variants is run through Recorder.flavor")
-
-
-# ------------------------------------------------------------------------------------------ packed weights
-@dataclass
-class ResnetW:
-    cin: int
-    cout: int
-    n1: Tuple[torch.Tensor, torch.Tensor]
-    conv1: PackedConv          # bias folded into the time projection
-    n2: Tuple[torch.Tensor, torch.Tensor]
-    conv2: PackedConv
-    shortcut: Optional[PackedConv]
-    temb_off: int              # column offset into the concatenated time-projection output
-
-
-@dataclass
-class BlockW:
-    """One BasicTransformerBlock."""
-    qkv: PackedConv            # LayerNorm norm1 folded in (pack_linear_ln)
-    out1: PackedConv
-    q2: PackedConv             # norm2 folded in
-    kv2: PackedConv
-    out2: PackedConv
-    ff1: PackedConv            # norm3 folded in, GEGLU tile-packed
-    ff2: PackedConv
-    kv_index: int              # index of this block's entries in a prompt's constants (PromptLayout)
-    # "absorbed" cross-attention (C >= XATTN_ABSORB_MIN_C): the text's key / value projections folded into the query and
-    # output weights, rebuilt per prompt on the GPU (vsd_xattn_fold); what that needs besides out2: device copies of
-    xa_raw: Optional[tuple] = None     # (raw to_q weight fp16 [C][C], norm2 gamma, norm2 beta)
-
-
-@dataclass
-class TransformerW:
-    """Transformer2DModel: GroupNorm, proj_in, `depth` blocks (1 for SD1.5; 2 / 10 for SDXL), proj_out."""
-    c: int
-    norm: Tuple[torch.Tensor, torch.Tensor]
-    proj_in: PackedConv
-    blocks: List[BlockW]
-    proj_out: PackedConv
-
-
-# Cross-attention as two GEMMs pays when one 128-column tile per head is not wider than the query projection it
-# replaces: 8 heads * 128 = 1024 columns against C (SD1.5: the 640- and 1280-wide levels; see pack_cross_attention)
-XATTN_ABSORB_MIN_C = 640
-
-
-class NetWeights:
-    """Device-resident, kernel-layout weights of one UNet-shaped network (UNet or ControlNet encoder)."""
-
-    def __init__(self, ops, cfg: UNetConfig, w: Dict[str, torch.Tensor], is_controlnet=False,
-                 cn_cfg: Optional[ControlNetConfig] = None):
-        self.ops, self.cfg, self.is_cn = ops, cfg, is_controlnet
-        self._w = w
-        self._temb_w, self._temb_b = [], []
-        self._temb_cols = 0
-        self.transformers: List[BlockW] = []  # every BasicTransformerBlock, in kv_cache order
-        dev = ops.to_device
-        ch = cfg.block_out_channels
-        self.conv_in = self._conv("conv_in", cin_pad=8)
-        self.time_l1 = self._lin("time_embedding.linear_1")
-        self.time_l2 = self._lin("time_embedding.linear_2")
-        self.cond_proj = self._lin("time_embedding.cond_proj") if cfg.cond_proj_dim else None
-        self.add_l1 = self._lin("add_embedding.linear_1") if cfg.add_time_dim else None
-        self.add_l2 = self._lin("add_embedding.linear_2") if cfg.add_time_dim else None
-        self.down: List[List[Tuple[ResnetW, Optional[TransformerW]]]] = []
-        self.downsamplers: List[Optional[PackedConv]] = []
-        cin = ch[0]
-        for i, cout in enumerate(ch):
-            blk = []
-            for j in range(cfg.layers_per_block):
-                r = self._resnet(f"down_blocks.{i}.resnets.{j}", cin if j == 0 else cout, cout)
-                t = (self._transformer(f"down_blocks.{i}.attentions.{j}", cout, cfg.transformer_depth[i])
-                     if cfg.down_attn[i] else None)
-                blk.append((r, t))
-            self.down.append(blk)
-            self.downsamplers.append(self._conv(f"down_blocks.{i}.downsamplers.0.conv") if i < len(ch) - 1 else None)
-            cin = cout
-        self.mid = (self._resnet("mid_block.resnets.0", ch[-1], ch[-1]),
-                    self._transformer("mid_block.attentions.0", ch[-1], cfg.mid_depth),
-                    self._resnet("mid_block.resnets.1", ch[-1], ch[-1]))
-        if not is_controlnet:
-            skips = skip_channels(cfg)
-            rev = list(reversed(ch))
-            self.up: List[List[Tuple[ResnetW, Optional[TransformerW]]]] = []
-            self.upsamplers: List[Optional[PackedConv]] = []
-            prev = ch[-1]
-            for i, cout in enumerate(rev):
-                blk = []
-                for j in range(cfg.layers_per_block + 1):
-                    sc = skips.pop()
-                    r = self._resnet(f"up_blocks.{i}.resnets.{j}", (prev if j == 0 else cout) + sc, cout)
-                    t = (self._transformer(f"up_blocks.{i}.attentions.{j}", cout, cfg.up_depth[i])
-                         if cfg.up_attn[i] else None)
-                    blk.append((r, t))
-                self.up.append(blk)
-                self.upsamplers.append(self._conv(f"up_blocks.{i}.upsamplers.0.conv") if i < len(rev) - 1 else None)
-                prev = cout
-            self.norm_out = self._norm("conv_norm_out")
-            self.conv_out = self._conv("conv_out")
+    def add_noise(self, r, x0, kind, draw, coef, batch, out):
+        hw, seeds, cs = self.hw, self.seeds, self.coef_stride
+        table = None if seeds is not None else (self.noise_ref if kind else self.noise)[draw]
+        if cs and seeds is not None:
+            r.add_noise_frames(x0, None, seeds, kind, draw, coef, cs, hw, batch, out)
+        elif cs:
+            r.add_noise_frames(x0, table, None, 0, 0, coef, cs, hw, batch, out)
+        elif seeds is not None:
+            r.add_noise_seeded(x0, seeds, kind, draw, coef, hw, batch, out)
         else:
-            cc = cn_cfg.cond_channels
-            p = "controlnet_cond_embedding"
-            self.cond_convs = [(self._conv(f"{p}.conv_in", cin_pad=8), 1)]
-            k = 0
-            for i in range(len(cc) - 1):
-                self.cond_convs.append((self._conv(f"{p}.blocks.{k}"), 1))
-                self.cond_convs.append((self._conv(f"{p}.blocks.{k + 1}"), 2))
-                k += 2
-            self.cond_out = self._conv(f"{p}.conv_out")
-            self.zero_convs = [self._conv(f"controlnet_down_blocks.{i}") for i in range(len(skip_channels(cfg)))]
-            self.zero_mid = self._conv("controlnet_mid_block")
-        # all per-ResnetBlock time projections as ONE linear layer: [sum Cout][temb_dim]
-        tw = pack_linear_cat(self._temb_w, self._temb_b)
-        self.temb_proj = self._to_dev(tw)
-        self._w = None
-        self._temb_w = self._temb_b = None
+            r.add_noise_dev(x0, table, coef, hw, batch, out)
 
-    # --- helpers
-    def _to_dev(self, p: PackedConv) -> PackedConv:
-        for f in ("weight", "bias", "ln_s", "ln_t", "weight_frag"):
-            v = getattr(p, f)
-            if v is not None:
-                setattr(p, f, self.ops.to_device(v.contiguous()))
-        return p
-
-    def _conv(self, name, cin_pad=None, with_bias=True) -> PackedConv:
-        b = self._w.get(name + ".bias") if with_bias else None
-        return self._to_dev(pack_conv(self._w[name + ".weight"], b, cin_pad=cin_pad))
-
-    def _lin(self, name) -> PackedConv:
-        return self._to_dev(pack_linear(self._w[name + ".weight"], self._w.get(name + ".bias")))
-
-    def _norm(self, name):
-        return (self.ops.to_device(self._w[name + ".weight"].half().contiguous()),
-                self.ops.to_device(self._w[name + ".bias"].half().contiguous()))
-
-    def _resnet(self, p, cin, cout) -> ResnetW:
-        off = self._temb_cols
-        self._temb_w.append(self._w[p + ".time_emb_proj.weight"])
-        # conv1's bias is folded into the time projection's bias: both are per-channel constants added
-        # to conv1's output before norm2 (ResnetBlock2D.forward).
-        self._temb_b.append((self._w[p + ".time_emb_proj.bias"].float() + self._w[p + ".conv1.bias"].float()))
-        self._temb_cols += cout
-        sc = self._conv(p + ".conv_shortcut") if (p + ".conv_shortcut.weight") in self._w else None
-        return ResnetW(cin, cout, self._norm(p + ".norm1"), self._conv(p + ".conv1", with_bias=False),
-                       self._norm(p + ".norm2"), self._conv(p + ".conv2"), sc, off)
-
-    def _transformer(self, p, c, depth=1) -> TransformerW:
-        w = self._w
-        blocks = []
-        for kb in range(depth):
-            b = f"{p}.transformer_blocks.{kb}"
-            ln = lambda n: (w[f"{b}.{n}.weight"], w[f"{b}.{n}.bias"])  # noqa: E731
-            qkv = self._to_dev(pack_linear_ln([w[f"{b}.attn1.to_q.weight"], w[f"{b}.attn1.to_k.weight"],
-                                               w[f"{b}.attn1.to_v.weight"]], None, *ln("norm1")))
-            q2 = self._to_dev(pack_linear_ln([w[f"{b}.attn2.to_q.weight"]], None, *ln("norm2")))
-            kv2 = self._to_dev(pack_linear_cat([w[f"{b}.attn2.to_k.weight"], w[f"{b}.attn2.to_v.weight"]]))
-            ff1 = self._to_dev(pack_geglu_ln(w[f"{b}.ff.net.0.proj.weight"], w[f"{b}.ff.net.0.proj.bias"], *ln("norm3")))
-            blk = BlockW(qkv, self._lin(b + ".attn1.to_out.0"), q2, kv2, self._lin(b + ".attn2.to_out.0"), ff1,
-                         self._lin(b + ".ff.net.2"), len(self.transformers))
-            heads = self.cfg.heads_for(c)
-            if c >= XATTN_ABSORB_MIN_C and c % heads == 0 and c % 64 == 0 and (c // heads) % 8 == 0:
-                dv = lambda t: self.ops.to_device(t.detach().to(torch.float16).contiguous())  # noqa: E731
-                blk.xa_raw = (dv(w[f"{b}.attn2.to_q.weight"]), dv(ln("norm2")[0]), dv(ln("norm2")[1]))
-            self.transformers.append(blk)
-            blocks.append(blk)
-        # use_linear_projection (SDXL): Linear on the token matrix == the 1x1 conv of SD1.5 in this layout
-        proj = self._lin if self.cfg.linear_proj else self._conv
-        tw = TransformerW(c, self._norm(p + ".norm"), proj(p + ".proj_in"), blocks, proj(p + ".proj_out"))
-        if c == getattr(self.ops, "TAIL_C", 0) and depth == 1:
-            # the fused per-token chains (csrc/fused_tail.hip) read these six matrices fragment-major
-            for pc in (blocks[0].out1, blocks[0].q2, blocks[0].out2, blocks[0].ff1, blocks[0].ff2, tw.proj_out):
-                pc.weight_frag = self.ops.to_device(add_frag(PackedConv(pc.weight.cpu(), None, pc.n, pc.k, pc.kp, pc.cin, pc.ksize)).weight_frag)
-        return tw
-
-
-class TAESDWeights:
-    def __init__(self, ops, w: Dict[str, torch.Tensor]):
-        self.ops = ops
-
-        def cv(name, cin_pad=None):
-            p = pack_conv(w[name + ".weight"], w.get(name + ".bias"), cin_pad=cin_pad)
-            p.weight = ops.to_device(p.weight)
-            if p.bias is not None:
-                p.bias = ops.to_device(p.bias)
-            return p
-
-        def blk(p):
-            return [cv(f"{p}.conv.{k}") for k in (0, 2, 4)]
-
-        e = "encoder.layers"
-        self.enc_in = cv(f"{e}.0", cin_pad=8)
-        self.enc_blocks0 = [blk(f"{e}.1")]
-        self.enc_stages = []
-        n = 2
-        for _ in range(3):
-            down = cv(f"{e}.{n}")
-            n += 1
-            bs = []
-            for _ in range(3):
-                bs.append(blk(f"{e}.{n}"))
-                n += 1
-            self.enc_stages.append((down, bs))
-        self.enc_out = cv(f"{e}.{n}")
-        d = "decoder.layers"
-        self.dec_in = cv(f"{d}.0", cin_pad=8)
-        self.dec_stages = []
-        n = 2
-        for nb in (3, 3, 3):
-            bs = []
-            for _ in range(nb):
-                bs.append(blk(f"{d}.{n}"))
-                n += 1
-            n += 1
-            up = cv(f"{d}.{n}")
-            n += 1
-            self.dec_stages.append((bs, up))
-        self.dec_last_block = blk(f"{d}.{n}")
-        n += 1
-        self.dec_out = cv(f"{d}.{n}")
-
-
-class PromptLayout:
-    """Byte layout of ONE prompt's device constants for a family of engines (same weights): per BasicTransformerBlock of the
-    UNet / ControlNet its cross-attention K [tl][C] and V^T [C][ldt], and for the wide blocks the "absorbed" query / output
-    weights (xa1: weights [heads*128][C] + ln_s / ln_t, xa2: weights [C][heads*128] + bias).  Everything lives in ONE
-    contiguous buffer (~40 MB for SD1.5 + ControlNet), so that switching an engine to another cached prompt is a single
-    device-to-device copy and a prompt cache entry is a single allocation."""
-
-    def __init__(self, nets, tl: int):
-        self.tl, self.ldt = tl, _ru(tl, 64)
-        self.items = {}   # (net index, block index, name) -> (offset, shape, dtype)
-        self.absorbed = set()
-        off = 0
-
-        def add(key, shape, dtype):
-            nonlocal off
-            n = 1
-            for d in shape:
-                n *= d
-            self.items[key] = (off, tuple(shape), dtype)
-            off = _ru(off + n * torch.empty(0, dtype=dtype).element_size(), 256)
-
-        for ni, net in enumerate(nets):
-            for bi, t in enumerate(net.transformers):
-                c = t.kv2.n // 2
-                add((ni, bi, "k"), (tl, c), torch.float16)
-                add((ni, bi, "vt"), (c, self.ldt), torch.float16)
-                if t.xa_raw is not None and tl <= 128:
-                    hg = net.cfg.heads_for(c) * 128
-                    self.absorbed.add((ni, bi))
-                    add((ni, bi, "xa1_w"), (hg, c), torch.float16)
-                    add((ni, bi, "xa1_s"), (hg,), torch.float32)
-                    add((ni, bi, "xa1_t"), (hg,), torch.float32)
-                    add((ni, bi, "xa2_w"), (c, hg), torch.float16)
-                    add((ni, bi, "xa2_b"), (c,), torch.float16)
-        self.nbytes = max(off, 256)
-
-
-class FramePromptLayout:
-    """Byte layout of the cross-attention constants of a launch whose B frames have prompts of their OWN (`Engine.prepare(frame_prompts=True)`):
-    per BasicTransformerBlock K as [B*tl][C], frame b owning rows [b*tl, (b+1)*tl), and V^T as [C][B*ldt], frame b owning columns
-    [b*ldt, (b+1)*ldt) with zeros beyond its tl keys -- what `attention(batch=B, k_brows=tl, vt_bcols=ldt)` reads.  No absorbed weights: they
-    would be per frame too (B weight sets per layer), so every cross-attention of such a program runs in the explicit form."""
-
-    def __init__(self, nets, tl: int, frames: int):
-        self.tl, self.ldt, self.frames = tl, _ru(tl, 64), int(frames)
-        self.items = {}
-        self.absorbed = frozenset()
-        off = 0
-        for ni, net in enumerate(nets):
-            for bi, t in enumerate(net.transformers):
-                c = t.kv2.n // 2
-                if c % 8:
-                    raise ValueError(f"frame_prompts: a {c}-wide transformer block: rows must be whole 16-byte chunks (C a multiple of 8)")
-                for name, shape in (("k", (self.frames * tl, c)), ("vt", (c, self.frames * self.ldt))):
-                    self.items[(ni, bi, name)] = (off, shape, torch.float16)
-                    off = _ru(off + shape[0] * shape[1] * 2, 256)
-        self.nbytes = max(off, 256)
-
-
-def prompt_segments(src: PromptLayout, dst: FramePromptLayout):
-    """The copy list of `vsd_prompt_install` (include/vsd.h vsd_prompt_seg) that puts a cache entry of layout `src` into ONE frame slot of a
-    block of layout `dst`: per tensor (src_off, dst_off, rows, row_bytes, dst_pitch, dst_frame_stride), bytes except the count `rows`.
-    K is one run; V^T is C rows of ALL ldt columns (the zero padding travels with the data) at the destination's pitch."""
-    if src.tl != dst.tl:
-        raise ValueError(f"a prompt of {src.tl} tokens into a per-frame block of {dst.tl}: all frames of a launch must have the same text length")
-    B, segs = dst.frames, []
-    for key, (doff, _dshape, _dt) in dst.items.items():
-        soff, sshape, _st = src.items[key]
-        if key[2] == "k":
-            n = sshape[0] * sshape[1] * 2
-            segs.append((soff, doff, 1, n, B * n, n))
+    def lcm_step(self, r, eps, cur, draw, coef, batch, nxt, den, dec_in):
+        hw, seeds, cs = self.hw, self.seeds, self.coef_stride
+        table = self.noise[draw] if seeds is None and draw else None
+        if cs and seeds is not None:  # (draw 0: the step adds no noise -- neither source)
+            r.lcm_step_frames(eps, cur, None, seeds if draw else None, 0, draw, coef, cs, hw, batch, nxt, den, dec_in)
+        elif cs:
+            r.lcm_step_frames(eps, cur, table, None, 0, 0, coef, cs, hw, batch, nxt, den, dec_in)
+        elif seeds is not None:
+            r.lcm_step_seeded(eps, cur, seeds, 0, draw, coef, hw, batch, nxt, den, dec_in)
         else:
-            c, ldt = sshape
-            segs.append((soff, doff, c, ldt * 2, B * ldt * 2, ldt * 2))
-    assert all(v % 16 == 0 for sg in segs for v in sg[:2] + sg[3:])
-    return segs
-
-
-class OptionLayout:
-    """Byte layout of the constants that depend on a frame's OPTIONS (`Engine.prepare(frame_options=True)`) for `frames` frames: per item a
-    run of `frames` slots of equal size, frame f owning bytes [off + f * size, off + (f + 1) * size) --
-      "coef": fp32 [coef_stride]: [0:2] the add_noise coefficients, [2 + 6i : 8 + 6i] the scheduler coefficients of step i (the layout of
-              the default program's constant block), padded to whole 16-byte units;
-      one item per network ("unet", "cn"): fp16 [n][cols], its per-step time-embedding projections (conv1's bias folded in).
-    frames = 1 is the layout of an option ENTRY (one schedule's constants, a cache entry); an engine's own block has its batch size.  Every
-    offset and size is a multiple of 16 bytes: a slot is installed by `prompt_install`, a segmented copy of 16-byte chunks."""
-
-    def __init__(self, n: int, cols: Dict[str, int], frames: int):
-        self.n, self.frames, self.cols = int(n), int(frames), dict(cols)
-        self.coef_stride = _ru(2 + 6 * self.n, 4)  # floats
-        self.items = {}  # name -> (offset, bytes per frame)
-        off = 0
-        for name, nb in [("coef", self.coef_stride * 4)] + [(k, self.n * c * 2) for k, c in self.cols.items()]:
-            if nb % 16:
-                raise ValueError(f"frame_options: {name}: {nb} bytes per frame: the time tables' columns must be a multiple of 8")
-            self.items[name] = (off, nb)
-            off = _ru(off + self.frames * nb, 256)
-        self.nbytes = max(off, 256)
-
-    def view(self, buf, name, frame: int = 0):
-        """frame `frame`'s slot of item `name` in `buf` (bytes of this layout): fp32 [coef_stride], or fp16 [n][cols]"""
-        off, nb = self.items[name]
-        raw = buf[off + frame * nb:off + (frame + 1) * nb]
-        return raw.view(torch.float32) if name == "coef" else raw.view(torch.float16).view(self.n, self.cols[name])
-
-
-def option_segments(src: OptionLayout, dst: OptionLayout):
-    """The copy list of `vsd_prompt_install` (include/vsd.h vsd_prompt_seg) that puts an option entry (layout `src`, one frame) into ONE frame
-    slot of an engine's block (layout `dst`): per item one run (src_off, dst_off, 1, bytes, frames * bytes, bytes)."""
-    if src.frames != 1 or src.n != dst.n or src.cols != dst.cols:
-        raise ValueError("an option entry of another schedule length or other networks than the block it is installed into")
-    segs = [(src.items[k][0], doff, 1, nb, dst.frames * nb, nb) for k, (doff, nb) in dst.items.items()]
-    assert all(v % 16 == 0 for sg in segs for v in sg[:2] + sg[3:])
-    return segs
-
-
-class OptionEntry:
-    """One schedule's constants in device memory (layout: OptionLayout with one frame): what every `strength` that gives these timesteps
-    shares.  Engines read THEIR OWN block; an entry is installed into a frame slot by copying."""
-
-    def __init__(self, layout: OptionLayout, buf, timesteps):
-        self.layout, self.buf, self.timesteps = layout, buf, tuple(timesteps)
-
-
-def controlnet_scales(nres: int, controlnet_scale: float):
-    """ControlNetModel guess mode: logspace(-1, 0, nres) * conditioning_scale (always on: lcm_controlnet.py:399,447), fp32"""
-    return torch.logspace(-1, 0, nres) * float(controlnet_scale)
-
-
-FRAME_OPTION_OPS = ("add_noise_frames", "lcm_step_frames", "groupnorm_addvec", "cn_merge_frames", "prompt_install")
-MAX_OPTION_ENTRIES = 64  # (at most 50 timestep tuples per `steps`; an entry is a few hundred KB)
-
-
-class PromptBlock:
-    """One prompt's constants in device memory (layout: PromptLayout).  Engines read THEIR OWN block (its addresses are in
-    their captured graphs); a cached prompt is installed by copying its block over the engine's."""
-
-    def __init__(self, ops, layout: PromptLayout):
-        self.layout = layout
-        self.buf = ops.zeros(layout.nbytes, dtype=torch.uint8)  # zero: V^T key padding and the unused rows of the xa weights
-        self._xa = {}
-        self.text = None
-
-    def view(self, ni, bi, name):
-        off, shape, dtype = self.layout.items[(ni, bi, name)]
-        n = 1
-        for d in shape:
-            n *= d
-        return self.buf[off:off + n * torch.empty(0, dtype=dtype).element_size()].view(dtype).view(*shape)
-
-    def kv(self, ni, bi):
-        return self.view(ni, bi, "k"), self.view(ni, bi, "vt")
-
-    def xa(self, ni, bi):
-        """(xa1, xa2) PackedConv pair of an absorbed block (views into this block), or None"""
-        if (ni, bi) not in self.layout.absorbed:
-            return None
-        got = self._xa.get((ni, bi))
-        if got is None:
-            w1, w2 = self.view(ni, bi, "xa1_w"), self.view(ni, bi, "xa2_w")
-            hg, c = w1.shape
-            x1 = PackedConv(w1, None, hg, c, c, c, 1, ln_s=self.view(ni, bi, "xa1_s"), ln_t=self.view(ni, bi, "xa1_t"), tile128=True)
-            x2 = PackedConv(w2, self.view(ni, bi, "xa2_b"), c, hg, hg, hg, 1)
-            got = self._xa[(ni, bi)] = (x1, x2)
-        return got
+            r.lcm_step_dev(eps, cur, table, coef, hw, batch, nxt, den, dec_in)
 
 
 class RefCtx:
@@ -525,65 +105,100 @@ class Engine:
                  guidance_scale: float = 7.5):
         self.ops = ops
         self.ucfg, self.ccfg, self.vcfg = unet_cfg, cn_cfg, vae_cfg
-        self.unet = NetWeights(ops, unet_cfg, w_unet)
-        self.cn = NetWeights(ops, cn_cfg.unet, w_cn, True, cn_cfg) if w_cn is not None else None
+        # (the width threshold is read from THIS module when an engine is made: tests lower `engine.XATTN_ABSORB_MIN_C`)
+        self.unet = NetWeights(ops, unet_cfg, w_unet, absorb_min_c=XATTN_ABSORB_MIN_C)
+        self.cn = NetWeights(ops, cn_cfg.unet, w_cn, True, cn_cfg, absorb_min_c=XATTN_ABSORB_MIN_C) if w_cn is not None else None
         self.vae = TAESDWeights(ops, w_vae)
+        # ---- what a family shares: everything a slot (`make_slot`) inherits besides the weights above
         self.guidance_scale = guidance_scale  # never forwarded by the reference (videopipeline.py:114-124): 7.5
         self.text = None
         self.added = None  # SDXL: (pooled text embeds, 6 time ids)
-        self.plan = None
-        self.graph = None
-        self.program = self.program_serial = None
-        self.seed_dev = self._seed_host = None  # `prepare(device_seed=True)`: one seed per frame of the launch, device buffer + pinned mirror
         self.use_graph = True
         self.is_slot = False
         self.batch = 1
-        self.overlap_controlnet = True  # record the ControlNet encoder for a second stream, parallel to the UNet encoder
+        # record the ControlNet encoder for a second stream, parallel to the UNet encoder (`VSD_OVERLAP_CN`: A/B switch; callers that
+        # set the attribute afterwards still win)
+        self.overlap_controlnet = _env_switch("VSD_OVERLAP_CN", True)
         self.overlap_launch = True      # ... and launch it that way by default (`launch(overlap=...)` decides per launch)
         # kernel choices of the plan: False = each layer's fastest form ALONE on an idle GPU (a lone launch: latency), True = the
         # form that costs least with four launch lanes busy (throughput; ops.HipOps.tune_conv).  Fixed per plan at `prepare`.
         self.tune_for_lanes = False
-        self.graph_serial = None
         # ... and, optionally, while that stream is otherwise idle: the ControlNet skip merges beside the mid block / decoder
         # start and Sobel + conditioning embedding beside the TAESD encoder (`use_side_stream`).  Measured on MI355X (512x512,
         # 4 steps): one frame alone 23.8 -> 23.2 ms, but with two launches in flight 97 -> 81 frames/s -- four busy hardware
         # queues instead of two cost more than the filled gaps give.  Round 4, launch streams on their own pipes: level either
         # way (one frame 47.8 vs 47.6 launches/s, 5 x 2 128.0 vs 128.4).  Off; `VSD_SIDE=1` switches it on.  (Round 2 also
         # moved the decoder's 1x1 shortcut convs there: 23.6 ms, removed.)
-        self.use_side_stream = False
-        import os as _os
-        if _os.environ.get("VSD_SIDE") is not None:  # A/B switch
-            self.use_side_stream = _os.environ.get("VSD_SIDE") == "1"
-        if _os.environ.get("VSD_OVERLAP_CN") is not None:  # A/B switch (callers that set the attribute afterwards still win)
-            self.overlap_controlnet = _os.environ.get("VSD_OVERLAP_CN") == "1"
-        self._ev_count = 0
+        self.use_side_stream = _env_switch("VSD_SIDE", False)
         # what a slot shares with its parent besides the weights: the per-plan constant block (schedule coefficients,
         # ControlNet scales) that the captured graphs READ, so that `update_options` reaches every graph at once
         self.shared = {}
         # what EVERY engine made from this one shares (weights aside): the prompt-constant layout and the default prompt
         # (`set_text_embeds`); an engine follows the default unless `use_prompt` gave it one of its own
         self.family = {}
-        self.pblock = None      # this engine's own prompt constants (the addresses its program / graph reads)
-        self._installed = None  # the PromptBlock whose bytes `pblock` currently holds
-        self._want = None       # `use_prompt`: this engine's prompt (None: the family default)
-        # `prepare(frame_prompts=True)`: `pblock` is a per-frame block (FramePromptLayout) instead
-        self.frame_prompts = False
-        self._want_list = None  # `use_prompts`: one PromptBlock per frame of the launch (None: `_want` / the default for every frame)
-        self._slot_src = []     # the PromptBlock whose K / V^T each frame slot of `pblock` holds (a reference: the source outlives its install)
-        # `prepare(frame_options=True)`: strength / controlnet_scale per frame of the launch (`use_options`)
-        self.frame_options = False
-        self.fo_layout = self.fo_buf = self.fo_scale = self._fo_scale_host = self._fo_scale_last = None
-        self._want_opts = None   # `use_options`: (OptionEntry, controlnet_scale) per frame (None: the plan's own options for every frame)
-        self._opt_slot_src = []  # the OptionEntry each frame slot of `fo_buf` holds
-        self._merge_tabs = []    # the segment tables of the recorded `cn_merge_frames` calls (their addresses are in the graph)
         self.absorb_cross_attention = True  # cross-attention of the wide blocks as two GEMMs (vsd_xattn_fold)
         self.use_fused_tail = True          # 320-wide blocks: per-token chains as fused launches (csrc/fused_tail.hip)
-        self.group_merges = not __import__("os").environ.get("VSD_NO_GROUP")  # the ControlNet merges of a step as two grouped launches
+        self.group_merges = not os.environ.get("VSD_NO_GROUP")  # the ControlNet merges of a step as two grouped launches
         # the one-stream form of the program runs the UNet and the ControlNet encoder of a step in lock step, twin layers as one
         # grid (`prepare`: both forms are recorded, `launch` picks)
-        self.twin_encoders = not __import__("os").environ.get("VSD_NO_TWIN")
-        self.group_shortcuts = not __import__("os").environ.get("VSD_NO_GROUP_SHORTCUT")  # (a ResnetBlock's shortcut conv in conv1's grid)
+        self.twin_encoders = not os.environ.get("VSD_NO_TWIN")
+        self.group_shortcuts = not os.environ.get("VSD_NO_GROUP_SHORTCUT")  # (a ResnetBlock's shortcut conv in conv1's grid)
         self.tail_b_min_rows = 1024         # ... the feed-forward chain from this many tokens per launch on (see _transformer)
+        # ---- what belongs to this engine alone
+        self._reset_own_state()
+
+    def _reset_own_state(self):
+        """EVERY attribute that belongs to one engine -- what two engines of a family running side by side on different lanes must not
+        share -- at its empty value.  `__init__` and `make_slot` call it; no other place creates an attribute of an engine."""
+        self._reset_plan_state()
+        # the prompt: outlives a plan (a `prepare` for the same text length keeps the block and what it holds)
+        self.pblock = None          # this engine's own prompt constants (the addresses its program / graph reads)
+        self._installed = None      # the PromptBlock whose bytes a single-prompt `pblock` currently holds
+        self._want = None           # `use_prompt`: this engine's prompt (None: the family default)
+        self._want_list = None      # `use_prompts`: one PromptBlock per frame of the launch (None: `_want` / the default for every frame)
+        self._prompt_slots = None   # FrameSlots of a per-frame `pblock` (`prepare(frame_prompts=True)`): the PromptBlock each slot holds
+        # device memory and pinned host memory that is reused from plan to plan
+        self._vt_pool = {}          # (C, columns, index) -> zero-padded V^T buffer of a self-attention, outside the rewound arena
+        self._stage = None          # (shape, pinned frame in, pinned frame out, event before the launch, event after it): `_staging`
+        self._raw_stage = None      # (pinned bytes, device bytes) of the crop boxes of camera frames: `_raw_staging`
+        self._i420_stage = None     # (device bytes, pinned bytes) of the I420 output: `_enqueue_i420`
+        # what the last submit / collect measured
+        self.last_gpu_ms = None         # the launch alone, between the events of `_stage`
+        self.last_upload_bytes = 0      # `submit_raw_i420`: bytes handed to the host-to-device copies
+        self.last_download_bytes = 0    # `collect_i420`: bytes brought back
+
+    def _reset_plan_state(self):
+        """The part of an engine's own state that ONE `prepare` makes: `prepare` starts from these values (after `_destroy_graphs`)."""
+        self.plan = None             # the prepared plan's description (what `prepare` returns)
+        self.program = None          # the recorded program: what a lone launch runs
+        self.program_serial = None   # ... and its one-stream form
+        self.graph = None            # the captured launch sequence of `program`
+        self.graph_serial = None     # ... of `program_serial` (the same object when the two forms do not differ)
+        self.arena = None            # the activations' bump allocator
+        self._vt_count = 0           # index of the next V^T buffer of a denoising step in `_vt_pool`
+        self.buffers = None          # name -> the program's persistent tensors (latents, eps, ...), for tests and probes
+        self.frame_u8 = None         # the launch's input frame(s)
+        self.out_u8 = None           # ... its output frame(s)
+        self.edge_u8 = None          # ... its Sobel edge map(s)
+        self.ref_u8 = None           # `ref_mode`: the reference image
+        self._ref_epoch = None       # ... and which reference image of the pipeline `ref_u8` holds (VideoSDPipeline sets it)
+        self.noise = None            # the host draws on the device (None: `device_seed`)
+        self.noise_ref = None        # `ref_mode`: the draws of the reference latents
+        self.seed_dev = None         # `device_seed`: one seed per frame of the launch
+        self._seed_host = None       # ... and its pinned mirror
+        self.frame_prompts = False   # `pblock` is a per-frame block (FramePromptLayout)
+        self.frame_options = False   # strength / controlnet_scale per frame of the launch (`use_options`)
+        self.fo_layout = None        # `frame_options`: the OptionLayout of this engine's own block, one slot per frame
+        self.fo_buf = None           # ... the block
+        self._option_slots = None    # ... its FrameSlots: the OptionEntry each slot holds
+        self._want_opts = None       # `use_options`: (OptionEntry, controlnet_scale) per frame (None: the plan's own options for every frame)
+        self.fo_scale = None         # `frame_options` with a ControlNet: fp32 [B][16] residual scales per frame
+        self._fo_scale_host = None   # ... their pinned mirror
+        self._fo_scale_last = None   # ... and what was last uploaded
+        self._merge_tabs = []        # the segment tables of the recorded `cn_merge_frames` calls (their addresses are in the graph)
+        self._cn_scale_consts = None  # the default program's fp32 [nres] residual scales, a view of shared["consts"]
+        self._twin_now = False       # this plan's one-stream form runs the encoders in lock step
+        self._i420_queued = False    # `rgb_to_i420` of `out_u8` is already queued behind the last launch
 
     def make_slot(self, share_plan: bool = True, lane: Optional[int] = None) -> "Engine":
         """A further engine on the same GPU and the same weights, with its own streams, arena, I/O buffers, prompt constants
@@ -597,34 +212,21 @@ class Engine:
         every session's frames go through the same actors).
         lane: the launch lane whose streams the engine uses (HipOps.clone; default: the next unused lane).  Engines of one lane
         take turns on its streams, engines of different lanes run side by side."""
-        e = Engine.__new__(Engine)
-        e.__dict__.update(self.__dict__)
+        e = copy.copy(self)  # what a family shares ...
         e.ops = self.ops.clone(lane)
-        e._vt_pool = {}
-        e.graph = None
-        e.graph_serial = None
-        e.plan = None
-        e._stage = None  # own pinned staging buffers and events (a copy of the parent's would be SHARED with it)
-        e._raw_stage = None
-        e.seed_dev = e._seed_host = None
-        e.pblock = None
-        e._installed = None
-        e._want = None
-        e._want_list = None
-        e._slot_src = []
-        e.frame_options = False
-        e.fo_layout = e.fo_buf = e.fo_scale = e._fo_scale_host = e._fo_scale_last = None
-        e._want_opts = None
-        e._opt_slot_src = []
-        e._merge_tabs = []
+        e._reset_own_state()  # ... and nothing of what is this engine's own
         e.is_slot = bool(share_plan)
         if not share_plan:
             e.shared = {}
         return e
 
     # ---------------------------------------------------------------- prompt-dependent constants
+    def _networks(self, use_controlnet: bool = True):
+        """(name, net) of the networks in play: the UNet, and the ControlNet when it is loaded and the plan uses it"""
+        return [("unet", self.unet)] + ([("cn", self.cn)] if use_controlnet and self.cn is not None else [])
+
     def _nets(self):
-        return [self.unet] + ([self.cn] if self.cn else [])
+        return [net for _name, net in self._networks()]
 
     def build_prompt(self, embeds: torch.Tensor) -> PromptBlock:
         """embeds: [77, cross_dim] (or [1,77,cross_dim]) -> a fresh PromptBlock: cross-attention K and V^T of every layer (the
@@ -683,7 +285,7 @@ class Engine:
 
     def _frame_sources(self, batch: int):
         """frame_prompts: the PromptBlock of every frame of a launch of `batch` frames, checked (count, one text length)"""
-        want = getattr(self, "_want_list", None)
+        want = self._want_list
         if want is None:
             d = self._want if self._want is not None else self.family.get("prompt")
             if d is None:
@@ -695,27 +297,24 @@ class Engine:
             raise ValueError(f"all frames of a launch must have the same text length, got {[b.layout.tl for b in want]}")
         return want
 
-    def _seg_table(self, src: PromptLayout, dst: FramePromptLayout):
-        """(device table, segments) of `prompt_install` for this pair of layouts: built once per family"""
+    def _seg_table(self, src, dst):
+        """(device table, segments) of `prompt_install` for this pair of layouts -- a prompt into a per-frame prompt block, an option entry
+        into a per-frame option block: built once per family"""
         tabs = self.family.setdefault("seg_tables", {})
         got = tabs.get((src, dst))
         if got is None:
-            segs = prompt_segments(src, dst)
+            segs = (option_segments if isinstance(dst, OptionLayout) else prompt_segments)(src, dst)
             got = tabs[(src, dst)] = (self.ops.to_device(torch.tensor(segs, dtype=torch.int64)), len(segs))
             self.ops.synchronize()  # (the other lanes' streams read it too)
         return got
 
     def _sync_prompt(self):
-        if getattr(self, "frame_prompts", False):
+        if self.frame_prompts:
             want = self._frame_sources(self.batch)
             lay = self.pblock.layout
             if want[0].layout.tl != lay.tl:
                 raise ValueError(f"the prompts' text length ({want[0].layout.tl}) differs from the one this plan was prepared for ({lay.tl}): prepare again")
-            for f, src in enumerate(want):
-                if src is not self._slot_src[f]:
-                    tab, nseg = self._seg_table(src.layout, lay)
-                    self.ops.prompt_install(src.buf, self.pblock.buf, tab, nseg, f)
-                    self._slot_src[f] = src
+            self._prompt_slots.install(self.ops, want, self._seg_table)
             return
         src = self._want if self._want is not None else self.family.get("prompt")
         if src is None:
@@ -731,14 +330,12 @@ class Engine:
         return 13 if self.cn is None else len(self.cn.zero_convs) + 1
 
     def _option_cols(self, use_controlnet: bool) -> Dict[str, int]:
-        return {name: net.temb_proj.n for name, net in [("unet", self.unet)] + ([("cn", self.cn)] if use_controlnet else [])}
+        return {name: net.temb_proj.n for name, net in self._networks(use_controlnet)}
 
     def option_entry(self, strength: float, steps: int, use_controlnet: bool = True) -> OptionEntry:
         """The constants of the schedule `(strength, steps)` as a cache entry, keyed by its TIMESTEPS (`lcm_timesteps` maps many strengths
         to one tuple): scheduler coefficients and both time tables in one device buffer, built once (~1 ms on the GPU: the ~10 tiny
         GEMMs of the time path) and kept in an LRU cache every engine of the family shares.  Touches nothing a running launch reads."""
-        from collections import OrderedDict
-
         sched = LCMSchedule(strength, steps)
         key = (tuple(int(t) for t in sched.timesteps), bool(use_controlnet))
         cache = self.family.setdefault("option_entries", OrderedDict())
@@ -750,13 +347,11 @@ class Engine:
             if lay is None:
                 lay = lays[(n, bool(use_controlnet))] = OptionLayout(n, self._option_cols(use_controlnet), 1)
             buf = self.ops.zeros(lay.nbytes, dtype=torch.uint8)
-            vals = list(sched.add_noise_coef())
-            for i in range(n):
-                vals += [float(x) for x in sched.step_coef(i)]
+            vals = schedule_constants(sched)
             host = torch.zeros(lay.coef_stride, dtype=torch.float32)
             host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
             self.ops.upload(lay.view(buf, "coef"), host)
-            for name, net in [("unet", self.unet)] + ([("cn", self.cn)] if use_controlnet else []):
+            for name, net in self._networks(use_controlnet):
                 self._time_embeddings(net, sched, lay.view(buf, name))
             self.ops.synchronize()  # (the other lanes' streams read it too)
             ent = cache[key] = OptionEntry(lay, buf, key[0])
@@ -787,16 +382,6 @@ class Engine:
                              f"{[s for s, _c in pairs]} give {counts}: another number of timesteps is another program")
         self._want_opts = [(self.option_entry(s, steps, self.plan["cn"]), c) for s, c in pairs]
 
-    def _opt_seg_table(self, src: OptionLayout, dst: OptionLayout):
-        """(device table, segments) of `prompt_install` for this pair of option layouts: built once per family"""
-        tabs = self.family.setdefault("opt_seg_tables", {})
-        got = tabs.get((src, dst))
-        if got is None:
-            segs = option_segments(src, dst)
-            got = tabs[(src, dst)] = (self.ops.to_device(torch.tensor(segs, dtype=torch.int64)), len(segs))
-            self.ops.synchronize()  # (the other lanes' streams read it too)
-        return got
-
     def _sync_options(self):
         """ahead of a launch of a `frame_options` engine: the frame slots whose entry changed, and the scales when any changed"""
         if not self.frame_options:
@@ -805,11 +390,7 @@ class Engine:
         want = self._want_opts
         if want is None:
             want = self._want_opts = [(self.option_entry(p["strength"], p["steps"], p["cn"]), float(p["cn_scale"]))] * p["batch"]
-        for f, (ent, _c) in enumerate(want):
-            if ent is not self._opt_slot_src[f]:
-                tab, nseg = self._opt_seg_table(ent.layout, self.fo_layout)
-                self.ops.prompt_install(ent.buf, self.fo_buf, tab, nseg, f)
-                self._opt_slot_src[f] = ent
+        self._option_slots.install(self.ops, [ent for ent, _c in want], self._seg_table)
         if self.fo_scale is not None:
             nres = self._nres()
             scales = [tuple(controlnet_scales(nres, c).tolist()) for _e, c in want]
@@ -1142,83 +723,88 @@ class Engine:
         h, skips = self._down_mid(r, net, step, x, sizes)
         return h, [(x, ch[0], 0)] + skips
 
-    def _controlnet_merge(self, r, cn_mid, cn_skips, u_mid, u_skips, sizes, scale):
+    def _merges(self, cn_mid, cn_skips, u_mid, u_skips, sizes):
+        """The 13 merges of a step in the order the decoder needs them -- the mid block's, then the skips' deepest first: (ControlNet
+        tensor, UNet tensor, zero-conv, channels, rows, scale column, level; None for the mid block)"""
+        net, B = self.cn, self.batch
+        hh, ww = sizes[-1]
+        yield cn_mid, u_mid, net.zero_mid, net.cfg.block_out_channels[-1], B * hh * ww, len(cn_skips), None
+        for i in reversed(range(len(cn_skips))):
+            (s, c, lvl), (us, uc, ulvl) = cn_skips[i], u_skips[i]
+            assert (c, lvl) == (uc, ulvl)
+            hh, ww = sizes[lvl]
+            yield s, us, net.zero_convs[i], c, B * hh * ww, i, lvl
+
+    def _can_group(self, todo):
+        """(a grouped launch exists for the buffer-load operand path only: every merge's channel count a multiple of 64 -- the shipped
+        SD1.5 / SDXL / MINI configs; a ControlNet of other widths takes the one-by-one merges: ADVICE r5)"""
+        return self.group_merges and all(m[3] % 64 == 0 for m in todo) and hasattr(self.ops, "conv_group")
+
+    @staticmethod
+    def _conv_groups(r, calls, gmax=7):
+        """conv calls that do not depend on each other as ONE grid per group of up to seven (vsd_conv_gemm_group), in the order given"""
+        for g0 in range(0, len(calls), gmax):
+            r.conv_group(calls[g0:g0 + gmax])
+
+    def _controlnet_merge(self, r, cn_mid, cn_skips, u_mid, u_skips, sizes):
         """The 13 zero-convs, each writing UNet tensor + scale_i * (conv + bias) in one epilogue
         (ControlNetModel's guess-mode scaling, always on in the reference: lcm_controlnet.py:399,447, and the
         `down_block_additional_residuals` / `mid_block_additional_residual` adds of UNet2DConditionModel)."""
-        a, net = self.arena, self.cn
-        nres = len(cn_skips) + 1
         if self.frame_options:
             return self._controlnet_merge_frames(r, cn_mid, cn_skips, u_mid, u_skips, sizes)
+        a = self.arena
+        todo = list(self._merges(cn_mid, cn_skips, u_mid, u_skips, sizes))
         sc = self._cn_scale_consts  # fp32 [nres] in device memory: logspace(-1, 0, nres) * controlnet_scale
-        assert sc.numel() >= nres
+        assert sc.numel() >= len(todo)
+        merged = [None] * len(cn_skips)
+
+        def merge(src, u, zc, c, rows, col, lvl):
+            o = a.alloc(rows, c)
+            return o, ((src, None, Geom.linear(rows), zc, o), dict(out_scale_dev=sc[col:col + 1], residual=u))
+
         # Only the mid-block merge is on the critical path; the decoder consumes the skips deepest first, one per ResnetBlock.
         # With the second stream free after the encoders' join, the 12 skip merges run there, in the order the decoder
         # needs them, each followed by a named event the consuming ResnetBlock waits for.
         side = self.overlap_controlnet and self.use_side_stream
-        merged = [None] * len(cn_skips)
-        # (a grouped launch exists for the buffer-load operand path only: every merge's channel count a multiple of 64 -- the shipped
-        #  SD1.5 / SDXL / MINI configs; a ControlNet of other widths takes the one-by-one merges below: ADVICE r5)
-        groupable = all(c % 64 == 0 for (_s, c, _l) in cn_skips) and net.cfg.block_out_channels[-1] % 64 == 0
-        if not side and self.group_merges and groupable and hasattr(self.ops, "conv_group"):
+        if not side and self._can_group(todo):
             # The 13 merges do not depend on each other and are small (11.5 us of a lone frame each as launches of their own: leaving
             # the 12 skip merges out of a 4-step frame takes 0.55 ms off it): ONE grid per group of up to eight of them
             # (vsd_conv_gemm_group) -- first the mid block's and the deepest skips' (what the decoder needs first), then the rest.
-            hh, ww = sizes[-1]
-            rows = self.batch * hh * ww
-            mid = a.alloc(rows, net.cfg.block_out_channels[-1])
-            calls = [((cn_mid, None, Geom.linear(rows), net.zero_mid, mid), dict(out_scale_dev=sc[nres - 1:nres], residual=u_mid))]
-            for i in reversed(range(len(cn_skips))):
-                (s, c, lvl), (us, uc, ulvl) = cn_skips[i], u_skips[i]
-                assert (c, lvl) == (uc, ulvl)
-                hh, ww = sizes[lvl]
-                rows = self.batch * hh * ww
-                o = a.alloc(rows, c)
-                calls.append(((s, None, Geom.linear(rows), net.zero_convs[i], o), dict(out_scale_dev=sc[i:i + 1], residual=us)))
-                merged[i] = (o, c, lvl, None)
-            gmax = 7
-            for g0 in range(0, len(calls), gmax):
-                r.conv_group(calls[g0:g0 + gmax])
+            calls, mid = [], None
+            for m in todo:
+                o, call = merge(*m)
+                calls.append(call)
+                if m[6] is None:
+                    mid = o
+                else:
+                    merged[m[5]] = (o, m[3], m[6], None)
+            self._conv_groups(r, calls)
             return mid, merged
         if side:
             r.signal("enc_done")
             r.use_stream(1)
             r.wait("enc_done")
-        for i in reversed(range(len(cn_skips))):
-            (s, c, lvl), (us, uc, ulvl) = cn_skips[i], u_skips[i]
-            assert (c, lvl) == (uc, ulvl)
-            hh, ww = sizes[lvl]
-            rows = self.batch * hh * ww
-            o = a.alloc(rows, c)
-            r.conv(s, None, Geom.linear(rows), net.zero_convs[i], o, out_scale_dev=sc[i:i + 1], residual=us)
+        for m in todo[1:]:
+            o, (aa, kk) = merge(*m)
+            r.conv(*aa, **kk)
             ev = None
             if side:
-                ev = f"skip{i}"
+                ev = f"skip{m[5]}"
                 r.signal(ev)
-            merged[i] = (o, c, lvl, ev)
+            merged[m[5]] = (o, m[3], m[6], ev)
         if side:
             r.use_stream(0)
-        hh, ww = sizes[-1]
-        rows = self.batch * hh * ww
-        c = net.cfg.block_out_channels[-1]
-        mid = a.alloc(rows, c)
-        r.conv(cn_mid, None, Geom.linear(rows), net.zero_mid, mid, out_scale_dev=sc[nres - 1:nres], residual=u_mid)
+        mid, (aa, kk) = merge(*todo[0])
+        r.conv(*aa, **kk)
         return mid, merged
 
     def _controlnet_merge_frames(self, r, cn_mid, cn_skips, u_mid, u_skips, sizes):
         """`frame_options`: the scale depends on the IMAGE, which an M tile of the zero-conv's GEMM does not know.  The zero-convs are
         recorded with out_scale = 1 and no residual (in the same grouped launches), and ONE `cn_merge_frames` launch then writes
         out = u + scale[image][i] * z for all 13 of them (include/vsd.h)."""
-        a, net, B = self.arena, self.cn, self.batch
-        nres = len(cn_skips) + 1
-        assert nres <= L.MERGE_SEG_MAX and nres <= self.fo_scale.shape[1]
-        hh, ww = sizes[-1]
-        todo = [(cn_mid, u_mid, net.zero_mid, net.cfg.block_out_channels[-1], B * hh * ww, nres - 1, None)]
-        for i in reversed(range(len(cn_skips))):
-            (s, c, lvl), (us, uc, ulvl) = cn_skips[i], u_skips[i]
-            assert (c, lvl) == (uc, ulvl)
-            hh, ww = sizes[lvl]
-            todo.append((s, us, net.zero_convs[i], c, B * hh * ww, i, lvl))
+        a, B = self.arena, self.batch
+        todo = list(self._merges(cn_mid, cn_skips, u_mid, u_skips, sizes))
+        assert len(todo) <= L.MERGE_SEG_MAX and len(todo) <= self.fo_scale.shape[1]
         calls, segs, keep = [], [], []
         mid, merged = None, [None] * len(cn_skips)
         for src, u, zc, c, rows, col, lvl in todo:
@@ -1232,11 +818,8 @@ class Engine:
                 mid = o
             else:
                 merged[col] = (o, c, lvl, None)
-        groupable = all(c % 64 == 0 for (_s, _u, _z, c, _r, _c, _l) in todo)
-        if self.group_merges and groupable and hasattr(self.ops, "conv_group"):
-            gmax = 7
-            for g0 in range(0, len(calls), gmax):
-                r.conv_group(calls[g0:g0 + gmax])
+        if self._can_group(todo):
+            self._conv_groups(r, calls)
         else:
             for aa, kk in calls:
                 r.conv(*aa, **kk)
@@ -1416,6 +999,35 @@ class Engine:
         frame's slice of the time table to its input (`groupnorm_addvec`), the zero-convs are recorded without scale and residual and one
         `cn_merge_frames` launch per step merges all 13 residuals with the frame's scales.  Composes with device_seed and frame_prompts;
         not with ref_mode or an SDXL UNet.  Default: one set of options per plan (`update_options`), as before."""
+        self._check_arguments(H, W, batch, use_controlnet, ref_mode, device_seed, frame_prompts, frame_options)
+        sched = LCMSchedule(strength, steps)
+        self._prepare_prompt_block(batch, frame_prompts)
+        # from here on the engine's previous plan is gone
+        self._destroy_graphs()
+        self._reset_plan_state()
+        self.batch = batch
+        self.frame_prompts, self.frame_options = bool(frame_prompts), bool(frame_options)
+        # The lock-step encoders are the one-stream form of EVERY program.  What a pair's grid looks like depends on the mode: a one-frame
+        # program (latency mode) takes the pair's own table entry, timed alone; a coalesced launch on busy lanes (throughput mode) runs
+        # the pair in the form its members have as launches of their own -- a latency-chosen form there occupies more workgroup-time
+        # than the two launches (profiles/round5f_pairs_at_5x4.txt).  Measured on one box with / without pairs: 1 x 4 89.7 / 83.5,
+        # 2 x 4 122.2 / 118.8, 3 x 4 133.8 / 131.3, 3 x 3 127.7 / 123.0, 4 x 4 138.8 / 138.3, 5 x 4 140.2 / 140.4 frames/s.
+        self._twin_now = self.twin_encoders
+        if hasattr(self.ops, "tune_mode"):
+            self.ops.tune_mode = 1 if self.tune_for_lanes else 0
+        if use_graph is not None:
+            self.use_graph = use_graph
+        coef = self._prepare_constants(sched, controlnet_scale, use_controlnet, ref_mode)
+        sops = self._prepare_noise(len(sched), H // 8, W // 8, ref_mode, device_seed)
+        self._record(sched, sops, coef, H, W, use_controlnet, ref_mode)
+        self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=len(sched), batch=batch,
+                         ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), frame_options=bool(frame_options), tuned_for_lanes=bool(self.tune_for_lanes),
+                         sizes=self._level_sizes(H, W), timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=self.arena.peak)
+        self._warm_up_and_capture(autotune)
+        return self.plan
+
+    def _check_arguments(self, H, W, batch, use_controlnet, ref_mode, device_seed, frame_prompts, frame_options):
+        """what `prepare` refuses, before it touches anything; the ops object's capabilities first (they read nothing but `self.ops`)"""
         if frame_options:
             missing = [f for f in FRAME_OPTION_OPS if not hasattr(self.ops, f)]
             if missing:
@@ -1428,20 +1040,18 @@ class Engine:
             raise ValueError("device_seed=True needs the ops add_noise_seeded and lcm_step_seeded, which this ops object does not have")
         if batch < 1:
             raise ValueError("batch must be >= 1")
-        self.batch = batch
-        # The lock-step encoders are the one-stream form of EVERY program.  What a pair's grid looks like depends on the mode: a one-frame
-        # program (latency mode) takes the pair's own table entry, timed alone; a coalesced launch on busy lanes (throughput mode) runs
-        # the pair in the form its members have as launches of their own -- a latency-chosen form there occupies more workgroup-time
-        # than the two launches (profiles/round5f_pairs_at_5x4.txt).  Measured on one box with / without pairs: 1 x 4 89.7 / 83.5,
-        # 2 x 4 122.2 / 118.8, 3 x 4 133.8 / 131.3, 3 x 3 127.7 / 123.0, 4 x 4 138.8 / 138.3, 5 x 4 140.2 / 140.4 frames/s.
-        self._twin_now = self.twin_encoders
-        if hasattr(self.ops, "tune_mode"):
-            self.ops.tune_mode = 1 if self.tune_for_lanes else 0
         if H % 8 or W % 8:
             raise ValueError("height and width must be multiples of 8 (TAESD / latent stride)")
-        src = self._want if self._want is not None else self.family.get("prompt")
-        if src is None and not (frame_prompts and getattr(self, "_want_list", None)):
+        if self._want is None and self.family.get("prompt") is None and not (frame_prompts and self._want_list):
             raise RuntimeError("set_text_embeds must be called before prepare")
+        if use_controlnet and self.cn is None:
+            raise RuntimeError("no ControlNet weights loaded")
+        if ref_mode and (batch != 1 or use_controlnet or (H // 8) * (W // 8) % 8):
+            raise ValueError("ref_mode: one frame per launch, no ControlNet (the reference-only pipeline has none), "
+                             "latent pixels a multiple of 8")
+
+    def _prepare_prompt_block(self, batch: int, frame_prompts: bool):
+        """`pblock` for the prompt(s) this engine is to run: kept, with what it holds, when the one of the plan before has the layout"""
         if frame_prompts:
             tl = self._frame_sources(batch)[0].layout.tl
             lays = self.family.setdefault("frame_layouts", {})  # (one layout OBJECT per (text length, frames), as for `layouts`)
@@ -1450,108 +1060,86 @@ class Engine:
                 lay = lays[(tl, batch)] = FramePromptLayout(self._nets(), tl, batch)
             if self.pblock is None or self.pblock.layout is not lay:
                 self.pblock = PromptBlock(self.ops, lay)
-                self._slot_src = [None] * batch
-        elif self.pblock is None or self.pblock.layout is not src.layout:
+                self._prompt_slots = FrameSlots(self.pblock.buf, lay)
+            return
+        src = self._want if self._want is not None else self.family.get("prompt")
+        if self.pblock is None or self.pblock.layout is not src.layout:
             self.pblock = PromptBlock(self.ops, src.layout)
-            self._installed = None
-        self.frame_prompts = bool(frame_prompts)
-        self.frame_options = bool(frame_options)
-        if use_controlnet and self.cn is None:
-            raise RuntimeError("no ControlNet weights loaded")
-        if ref_mode and (batch != 1 or use_controlnet or (H // 8) * (W // 8) % 8):
-            raise ValueError("ref_mode: one frame per launch, no ControlNet (the reference-only pipeline has none), "
-                             "latent pixels a multiple of 8")
-        if use_graph is not None:
-            self.use_graph = use_graph
+            self._installed = self._prompt_slots = None
+
+    def _prepare_constants(self, sched: LCMSchedule, controlnet_scale: float, use_controlnet: bool, ref_mode: bool):
+        """Per-plan constants the captured graph reads from device memory: [0:2] add_noise coefficients, [2 + 6i : 8 + 6i]
+        the scheduler coefficients of step i, then the 13 ControlNet residual scales; plus the time-embedding projections
+        of every step.  `update_options` rewrites them in place -- a new strength / controlnet_scale needs no re-capture.
+        -> the coefficients as the program reads them (`frame_options`: frame 0's)."""
+        ops, n, B = self.ops, len(sched), self.batch
+        ncn = 16
+        if self.frame_options:
+            # this engine's OWN blocks, one slot per frame: the program records frame 0's addresses and the strides; `_sync_options` fills
+            # the slots ahead of every launch (before the warm-up run, with the options `prepare` was given)
+            self.fo_layout = OptionLayout(n, self._option_cols(use_controlnet), B)
+            self.fo_buf = ops.zeros(self.fo_layout.nbytes, dtype=torch.uint8)
+            self._option_slots = FrameSlots(self.fo_buf, self.fo_layout)
+            if use_controlnet:
+                assert self._nres() <= ncn
+                self.fo_scale = ops.zeros(B, ncn, dtype=torch.float32)
+                self._fo_scale_host = torch.zeros(B, ncn, dtype=torch.float32, pin_memory=torch.cuda.is_available())
+            self.shared["n"] = n
+            return self.fo_layout.view(self.fo_buf, "coef")
+        c = self.shared.get("consts")
+        if self.is_slot:  # computed by the parent engine's prepare / update_options
+            assert c is not None and self.shared.get("n") == n, "prepare the parent engine with the same schedule first"
+        else:
+            if c is None or self.shared.get("n") != n:
+                self.shared["consts"] = c = ops.zeros(2 + 6 * n + ncn, dtype=torch.float32)
+                self.shared["n"] = n
+            temb = self.shared.setdefault("temb", {})
+            for name, net in self._networks(use_controlnet) + ([("ref", self.unet)] if ref_mode else []):
+                if name not in temb or temb[name].shape[0] != n:
+                    temb[name] = ops.zeros(n, net.temb_proj.n)
+            self.shared["ref_mode"] = bool(ref_mode)
+            self._write_constants(sched, controlnet_scale, use_controlnet)
+        self._cn_scale_consts = c[2 + 6 * n:]
+        return c
+
+    def _prepare_noise(self, n: int, h0: int, w0: int, ref_mode: bool, device_seed: bool) -> SchedulerOps:
+        """Where the noise comes from, chosen once per plan.  Default: the reference resets the global CPU generator to a
+        fresh-Generator state on every frame (videopipeline.py:126), so for a fixed shape the draws are the same every frame."""
         ops = self.ops
-        sched = LCMSchedule(strength, steps)
-        n = len(sched)
-        h0, w0 = H // 8, W // 8
-        sizes = [(h0, w0)]
+        cstride = self.fo_layout.coef_stride if self.frame_options else 0
+        if device_seed:
+            # one seed per frame of the launch, u32 (low, high) pairs = little-endian u64: this engine's own (a slot has its own)
+            self.seed_dev = ops.zeros(self.batch, dtype=torch.int64)
+            self._seed_host = torch.zeros(self.batch, dtype=torch.int64, pin_memory=torch.cuda.is_available())
+            return SchedulerOps(h0 * w0, seeds=self.seed_dev, coef_stride=cstride)
+        draws, ref_draws = self.host_noise(n, h0, w0, ref=ref_mode)
+        self.noise = ops.to_device(draws)
+        if ref_draws is not None:
+            self.noise_ref = ops.to_device(ref_draws)
+        return SchedulerOps(h0 * w0, noise=self.noise, noise_ref=self.noise_ref, coef_stride=cstride)
+
+    def _level_sizes(self, H: int, W: int):
+        """(height, width) of the latents at every level of the UNet"""
+        sizes = [(H // 8, W // 8)]
         for _ in range(len(self.ucfg.block_out_channels) - 1):
             ph, pw_ = sizes[-1]
             sizes.append(((ph + 1) // 2, (pw_ + 1) // 2))
+        return sizes
+
+    def _record(self, sched: LCMSchedule, sops: SchedulerOps, c, H: int, W: int, use_controlnet: bool, ref_mode: bool):
+        """arena, I/O tensors and the static program, in both forms"""
+        ops, B, n = self.ops, self.batch, len(sched)
+        sizes = self._level_sizes(H, W)
+        h0, w0 = sizes[0]
         hw0 = h0 * w0
-        self._destroy_graphs()
-        self.arena = Arena(ops, chunk_bytes=max(256 << 20, _ru(batch * H * W * 64 * 2, 1 << 20)))  # >= one TAESD tensor
-        self._vt_pool, self._vt_count = getattr(self, "_vt_pool", {}), 0
-        # persistent per-frame I/O and constants
-        B = batch
+        self.arena = a = Arena(ops, chunk_bytes=max(256 << 20, _ru(B * H * W * 64 * 2, 1 << 20)))  # >= one TAESD tensor
+        # persistent per-frame I/O
         frame_b = ops.zeros(B, H, W, 3, dtype=torch.uint8)
         out_b = ops.zeros(B, H, W, 3, dtype=torch.uint8)
         # public I/O buffers: [H][W][3] for a single frame (as before), [B][H][W][3] for a batch
         self.frame_u8 = frame_b[0] if B == 1 else frame_b
         self.out_u8 = out_b[0] if B == 1 else out_b
         self.edge_u8 = ops.zeros(B * H * W, dtype=torch.uint8)
-        # Per-plan constants the captured graph reads from device memory: [0:2] add_noise coefficients, [2 + 6i : 8 + 6i]
-        # the scheduler coefficients of step i, then the 13 ControlNet residual scales; plus the time-embedding projections
-        # of every step.  `update_options` rewrites them in place -- a new strength / controlnet_scale needs no re-capture.
-        ncn = 16
-        self.fo_layout = self.fo_buf = self.fo_scale = self._fo_scale_host = self._fo_scale_last = None
-        self._want_opts, self._opt_slot_src, self._merge_tabs = None, [None] * B, []
-        if frame_options:
-            # this engine's OWN blocks, one slot per frame: the program records frame 0's addresses and the strides; `_sync_options` fills
-            # the slots ahead of every launch (here, before the warm-up run, with the options `prepare` was given)
-            self.fo_layout = OptionLayout(n, self._option_cols(use_controlnet), B)
-            self.fo_buf = ops.zeros(self.fo_layout.nbytes, dtype=torch.uint8)
-            c = self.fo_layout.view(self.fo_buf, "coef")
-            if use_controlnet:
-                assert self._nres() <= ncn
-                self.fo_scale = ops.zeros(B, ncn, dtype=torch.float32)
-                self._fo_scale_host = torch.zeros(B, ncn, dtype=torch.float32, pin_memory=torch.cuda.is_available())
-            self.shared["n"] = n
-        elif self.is_slot:  # computed by the parent engine's prepare / update_options
-            c = self.shared.get("consts")
-            assert c is not None and self.shared.get("n") == n, "prepare the parent engine with the same schedule first"
-        else:
-            c = self.shared.get("consts")
-            if c is None or self.shared.get("n") != n:
-                self.shared["consts"] = c = ops.zeros(2 + 6 * n + ncn, dtype=torch.float32)
-                self.shared["n"] = n
-            temb = self.shared.setdefault("temb", {})
-            for name, net in [("unet", self.unet)] + ([("cn", self.cn)] if use_controlnet else []) + ([("ref", self.unet)] if ref_mode else []):
-                if name not in temb or temb[name].shape[0] != n:
-                    temb[name] = ops.zeros(n, net.temb_proj.n)
-            self.shared["ref_mode"] = bool(ref_mode)
-            self._write_constants(sched, controlnet_scale, use_controlnet)
-        self._cn_scale_consts = None if frame_options else c[2 + 6 * n:]
-        # noise draws: the reference resets the global CPU generator to a fresh-Generator state on every
-        # frame (videopipeline.py:126), so for a fixed shape the draws are the same every frame.
-        # Where the noise comes from is chosen here, once: add_noise(r, x0, kind, draw, coef, batch, out) and lcm_step(r, eps, cur, draw,
-        # coef, batch, nxt, den, dec_in) record the scheduler ops of either source (include/vsd.h: kind 0 draw d = noise[d], kind 1 draw
-        # d = noise_ref[d]; a step with draw 0 adds none).
-        ref_draws = None
-        cstride = self.fo_layout.coef_stride if frame_options else 0  # floats between two frames' coefficients
-        if device_seed:
-            # one seed per frame of the launch, u32 (low, high) pairs = little-endian u64: this engine's own (a slot has its own)
-            self.noise = self.noise_ref = None
-            self.seed_dev = seeds = ops.zeros(B, dtype=torch.int64)
-            self._seed_host = torch.zeros(B, dtype=torch.int64, pin_memory=torch.cuda.is_available())
-
-            def add_noise(r, x0, kind, draw, coef, batch, out):
-                if frame_options:
-                    return r.add_noise_frames(x0, None, seeds, kind, draw, coef, cstride, hw0, batch, out)
-                r.add_noise_seeded(x0, seeds, kind, draw, coef, hw0, batch, out)
-
-            def lcm_step(r, eps, cur, draw, coef, batch, nxt, den, dec_in):
-                if frame_options:  # (draw 0: the step adds no noise -- neither source)
-                    return r.lcm_step_frames(eps, cur, None, seeds if draw else None, 0, draw, coef, cstride, hw0, batch, nxt, den, dec_in)
-                r.lcm_step_seeded(eps, cur, seeds, 0, draw, coef, hw0, batch, nxt, den, dec_in)
-        else:
-            self.seed_dev = self._seed_host = None
-            draws, ref_draws = self.host_noise(n, h0, w0, ref=ref_mode)
-            self.noise = ops.to_device(draws)
-
-            def add_noise(r, x0, kind, draw, coef, batch, out):
-                if frame_options:
-                    return r.add_noise_frames(x0, self.noise[draw], None, 0, 0, coef, cstride, hw0, batch, out)
-                r.add_noise_dev(x0, (self.noise_ref if kind else self.noise)[draw], coef, hw0, batch, out)
-
-            def lcm_step(r, eps, cur, draw, coef, batch, nxt, den, dec_in):
-                if frame_options:
-                    return r.lcm_step_frames(eps, cur, self.noise[draw] if draw else None, None, 0, 0, coef, cstride, hw0, batch, nxt, den, dec_in)
-                r.lcm_step_dev(eps, cur, self.noise[draw] if draw else None, coef, hw0, batch, nxt, den, dec_in)
-        a = self.arena
         enc_in = a.alloc(B * H * W, 8)
         x0 = a.alloc(B * hw0, 8)
         lat = [a.alloc(B * hw0, 8), a.alloc(B * hw0, 8)]
@@ -1566,7 +1154,6 @@ class Engine:
         img = lambda t, b, n: t[b * n:(b + 1) * n]  # noqa: E731  rows of image b
         r.preprocess_rgb(frame_b, B * H, W, enc_in)
         cond_emb = None
-        self._ev_count = 0
         if use_controlnet:
             ctrl = a.alloc(B * H * W, 8)
             side0 = self.overlap_controlnet and self.use_side_stream
@@ -1583,8 +1170,6 @@ class Engine:
         if ref_mode:
             ref_b = ops.zeros(1, H, W, 3, dtype=torch.uint8)
             self.ref_u8 = ref_b[0]
-            if ref_draws is not None:
-                self.noise_ref = ops.to_device(ref_draws)
             ref_in, ref_x0, ref_xt, ref_eps = a.alloc(H * W, 8), a.alloc(hw0, 8), a.alloc(hw0, 8), a.alloc(hw0, 8)
             for t in (ref_x0, ref_xt, ref_eps):
                 ops.zero_(t)
@@ -1592,7 +1177,7 @@ class Engine:
             self._encode(r, ref_in, H, W, ref_x0)
             self.buffers["ref_x0"] = ref_x0
         # every frame gets the same draws: the reference resets its RNG per frame
-        add_noise(r, x0, 0, 0, c[0:2], B, lat[0])
+        sops.add_noise(r, x0, 0, 0, c[0:2], B, lat[0])
         mark = a.mark()
         for i in range(n):
             a.rewind(mark)
@@ -1625,12 +1210,12 @@ class Engine:
                     r.variants(two.calls, twin.calls)
                 else:
                     r.variants(two.calls, two.calls)
-                u_mid, u_skips = self._controlnet_merge(r, cn_mid, cn_skips, u_mid, u_skips, sizes, controlnet_scale)
+                u_mid, u_skips = self._controlnet_merge(r, cn_mid, cn_skips, u_mid, u_skips, sizes)
             elif ref_mode:
                 rc = RefCtx(self.ucfg)
                 # ref_xt = add_noise(ref latents, fresh draw, t_i) (lcm_reference_pipeline.py:861-871); the coefficients of
                 # timestep t_i are the first two of the step's scheduler coefficients
-                add_noise(r, ref_x0, 1, i, c[2 + 6 * i:4 + 6 * i], 1, ref_xt)  # (kind 1: the reference latents' draws, one per step)
+                sops.add_noise(r, ref_x0, 1, i, c[2 + 6 * i:4 + 6 * i], 1, ref_xt)  # (kind 1: the reference latents' draws, one per step)
                 w_mid, w_skips = self._unet_encoder(r, i, ref_xt, sizes, ref=rc, temb=self.shared["temb"]["ref"])
                 self._unet_decoder(r, i, w_mid, w_skips, sizes, ref_eps, ref=rc, temb=self.shared["temb"]["ref"])
                 rc.mode = "read"
@@ -1640,17 +1225,17 @@ class Engine:
             self._unet_decoder(r, i, u_mid, u_skips, sizes, eps, ref=rc if ref_mode else None)
             last = i == n - 1
             # (draw i + 1; 0: a one-step schedule adds none)
-            lcm_step(r, eps, cur, i + 1 if sched.multistep else 0, c[2 + 6 * i:8 + 6 * i], B, nxt, den, dec_in if last else None)
+            sops.lcm_step(r, eps, cur, i + 1 if sched.multistep else 0, c[2 + 6 * i:8 + 6 * i], B, nxt, den, dec_in if last else None)
         self._decode(r, dec_in, h0, w0, dec_out)
         r.postprocess_rgb(dec_out, 8, B * H * W, out_b)
         # program: what a lone launch runs (the ControlNet encoder on the side stream when `overlap_controlnet`);
         # program_serial: everything on the lane's own stream (the encoders in lock step when `twin_encoders`)
         self.program = r.flavor(0 if self.overlap_controlnet or not self._twin_now else 1)
         self.program_serial = r.flavor(1) if self._twin_now and self.overlap_controlnet and use_controlnet else self.program
-        self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=n, batch=B,
-                         ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), frame_options=bool(frame_options), tuned_for_lanes=bool(self.tune_for_lanes),
-                         sizes=sizes, timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=a.peak)
-        # per-shape kernel configuration (timed once per shape, cached in ops.tile_override), warm-up, capture
+
+    def _warm_up_and_capture(self, autotune: bool):
+        """per-shape kernel configuration (timed once per shape, cached in ops.tile_override), warm-up, capture"""
+        ops = self.ops
         torch.cuda.synchronize() if torch.cuda.is_available() else None  # allocation fills vs. kernel streams
         self._sync_prompt()
         self._sync_options()
@@ -1668,157 +1253,20 @@ class Engine:
             self.plan["graphs"], self.plan["edges"] = ops.seq_count(self.graph)
             two_forms = self.plan["edges"] or self.program_serial is not self.program
             self.graph_serial = self._capture(self.program_serial, serial=True) if two_forms else self.graph
-        return self.plan
 
-    SYNC_OPS = ("use_stream", "fork", "join", "signal", "wait")
-
-    @staticmethod
-    def flat_calls(calls):
-        """the recorded calls as single-op calls: the members of pairs and groups one by one (analysis scripts)"""
-        for fn, a, k in calls:
-            if fn.__name__ == "pair":
-                yield a[0]
-                yield a[1]
-            elif fn.__name__ == "conv_group":
-                for aa, kk in a[0]:
-                    yield (fn.__self__.conv, aa, kk)
-            else:
-                yield (fn, a, k)
+    SYNC_OPS = SYNC_OPS
+    flat_calls = staticmethod(flat_calls)
 
     def launches_by_kind(self, serial: bool = False):
-        """kernel launches one replay of the recorded program (serial: of its one-stream form) issues, by kind ("pair_*": two twin calls in one grid;
-        "convs_in_groups" counts members, not launches) -> (total, {kind: launches})"""
-        ops, kinds = self.ops, {}
-
-        def count(name, n=1):
-            if n:
-                kinds[name] = kinds.get(name, 0) + n
-
-        def gn_launches(a, k=None):  # (csrc/norm.hip gn_try_fused: one launch for small images, else statistics + apply)
-            if hasattr(ops, "groupnorm_launches"):  # (the library's own decision; the rule below serves the CPU op emulator of the tests)
-                return ops.groupnorm_launches(a[2], a[3], a[4], a[5], (k or {}).get("batch", 1))
-            c, hw, groups = a[2] + a[3], a[4], a[5]
-            cpg = c // groups
-            fused = ((hw <= 256 and cpg <= 40) or (hw <= 1024 and cpg <= 20)) and cpg in (40, 8, 16, 20, 4, 12, 10, 2, 6)
-            return 1 if fused else 2
-
-        def table(key):
-            ent = ops.tile_override.get(key)
-            if ent is None and key[-1] == 1:
-                ent = ops.tile_override.get(key[:-1] + (0,))
-            return ent
-
-        def conv_reducer(a, k):
-            ent = table(ops.conv_key_of(a[2], a[3], k))
-            return int(ent is not None and ent[1] > 1 and not ent[2] and not a[3].tile128)
-
-        for fn, a, k in (self.program_serial if serial else self.program).calls:
-            name = fn.__name__
-            if name in self.SYNC_OPS:
-                continue
-            if name == "pair":
-                (fa, aa, ka), (fb, ab, kb) = a
-                op = fa.__name__
-                if op == "conv":
-                    sp = ops.pair_split(aa, ka, ab, kb)
-                    ent = table(ops.group_key([(aa, ka), (ab, kb)], sp)) if sp is not None else (ops.GROUP_ALONE,)
-                    if sp is not None and getattr(ops, "tune_mode", 0) == 1:  # (throughput mode: the members' own form, ops.pair)
-                        ent = ops._pair_default
-                    if ent is None:
-                        ent = (0, sp, True, 3)
-                    if ent[0] != ops.GROUP_ALONE:
-                        count("pair_conv")
-                        count("pair_splitk_reduce", int(ent[1] > 1 and not ent[2]))
-                    else:
-                        count("conv", 2)
-                        count("splitk_reduce", conv_reducer(aa, ka) + conv_reducer(ab, kb))
-                elif op == "groupnorm":
-                    count("pair_groupnorm")
-                    count("pair_gn_second", gn_launches(aa, ka) - 1)
-                elif op == "groupnorm_addvec":  # (src, addvec, ld, c, hw, groups, ...)
-                    count("pair_groupnorm_addvec")
-                    count("pair_gn_second", gn_launches((None, None, aa[3], 0, aa[4], aa[5]), ka) - 1)
-                else:
-                    count("pair_" + op)
-                continue
-            if name == "conv_group":
-                split = k.get("split")
-                own = ops.own_splits(a[0]) if split == getattr(ops, "OWN_SPLIT", None) and hasattr(ops, "own_splits") else None
-                ent = table(ops.group_key(a[0], split)) if hasattr(ops, "group_key") else None
-                if (split is not None and own is None) or (ent is not None and ent[0] == ops.GROUP_ALONE):
-                    for aa, kk in a[0]:  # (a group whose table entry -- or a member's own form -- sends the members out alone)
-                        count("conv")
-                        count("splitk_reduce", conv_reducer(aa, kk))
-                    continue
-                count(name)
-                count("convs_in_groups", len(a[0]))
-                if ent is not None and not ent[2] and ((own and max(own) > 1) or (not own and ent[1] > 1)):
-                    count("group_splitk_reduce")
-                continue
-            count(name)
-            if name == "conv":
-                count("splitk_reduce", conv_reducer(a, k))
-            elif name == "groupnorm":
-                count("gn_second", gn_launches(a, k) - 1)
-            elif name == "groupnorm_addvec":
-                count("gn_second", gn_launches((None, None, a[3], 0, a[4], a[5]), k) - 1)
-        return sum(v for k, v in kinds.items() if k != "convs_in_groups"), kinds
+        """kernel launches one replay of the recorded program (serial: of its one-stream form) issues, by kind -> (total, {kind: launches})"""
+        return launches_by_kind(self.ops, self.program_serial if serial else self.program)
 
     def _capture(self, r: Recorder, serial: bool = False):
-        """serial=True: every call on stream 0, no edges (the program's fork / join / signal / wait markers are dropped: in one
-        in-order stream they hold by construction) -- one graph.
-        The recorded program -> a launch sequence (include/vsd.h vsd_seq): every run of kernel calls on one stream becomes ONE
-        single-branch hipGraph on that stream, every fork / join / signal / wait an event edge between the two streams, issued
-        in program order by `vsd_seq_launch`.  A program without a second stream is one graph, as before.  (One graph with
-        parallel branches is what rounds 1-3 captured; on this runtime two such graphs in flight serialise -- DESIGN.md
-        section 3, "launches in flight".)"""
-        ops = self.ops
-        seq = ops.seq_create()
-        cur, run, names = 0, [], {}
-
-        def flush():
-            nonlocal run
-            if run:
-                ops.seq_capture_begin(cur)
-                try:
-                    for fn, a, k in run:
-                        fn(*a, **k)
-                finally:
-                    ops.seq_capture_end(seq, cur)
-                run = []
-
-        try:
-            for fn, a, k in r.calls:
-                name = getattr(fn, "__name__", "")
-                if name not in self.SYNC_OPS:
-                    run.append((fn, a, k))
-                    continue
-                if serial:
-                    continue
-                if name == "use_stream":
-                    if a[0] != cur:
-                        flush()
-                        cur = a[0]
-                    continue
-                flush()
-                if name == "fork":
-                    ops.seq_wait(seq, 1, ops.seq_record(seq, 0))
-                elif name == "join":
-                    ops.seq_wait(seq, 0, ops.seq_record(seq, 1))
-                elif name == "signal":
-                    names[a[0]] = ops.seq_record(seq, cur)
-                else:
-                    ops.seq_wait(seq, cur, names[a[0]])
-            flush()
-        except Exception:
-            ops.use_stream(0)
-            ops.seq_destroy(seq)
-            raise
-        ops.use_stream(0)
-        return seq
+        """the recorded program -> a launch sequence (program.capture)"""
+        return capture(self.ops, r, serial)
 
     def _destroy_graphs(self):
-        g, gs = self.graph, getattr(self, "graph_serial", None)
+        g, gs = self.graph, self.graph_serial
         self.graph = self.graph_serial = None
         if g is not None:
             self.ops.seq_destroy(g)
@@ -1827,18 +1275,12 @@ class Engine:
 
     def _write_constants(self, sched: LCMSchedule, controlnet_scale: float, use_controlnet: bool):
         """Schedule- and option-dependent constants -> the device block / time-embedding tables the graphs read."""
-        n = len(sched)
-        vals = list(sched.add_noise_coef())
-        for i in range(n):
-            vals += [float(x) for x in sched.step_coef(i)]
-        nres = 13 if self.cn is None else len(self.cn.zero_convs) + 1
-        # ControlNetModel guess mode: logspace(-1, 0, 13) * conditioning_scale (always on: lcm_controlnet.py:399,447)
-        vals += (torch.logspace(-1, 0, nres) * float(controlnet_scale)).tolist()
+        vals = schedule_constants(sched) + controlnet_scales(self._nres(), controlnet_scale).tolist()
         c = self.shared["consts"]
         host = torch.zeros(c.numel(), dtype=torch.float32)
         host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
         self.ops.upload(c, host)
-        for name, net in [("unet", self.unet)] + ([("cn", self.cn)] if (use_controlnet and self.cn is not None) else []):
+        for name, net in self._networks(use_controlnet):
             self._time_embeddings(net, sched, self.shared["temb"][name])
         if self.shared.get("ref_mode"):  # the reference-only WRITE pass: same timesteps, no guidance embedding
             self._time_embeddings(self.unet, sched, self.shared["temb"]["ref"], use_cond=False)
@@ -1913,7 +1355,7 @@ class Engine:
         """Pinned host buffers of this plan's frame(s): H2D / D2H run as asynchronous DMA on the kernel stream instead of
         going through the runtime's pageable-memory staging copies."""
         key = tuple(self.frame_u8.shape)
-        st = getattr(self, "_stage", None)
+        st = self._stage
         if st is None or st[0] != key:
             pin = torch.cuda.is_available()
             st = (key, torch.empty(key, dtype=torch.uint8, pin_memory=pin), torch.empty(key, dtype=torch.uint8, pin_memory=pin),
@@ -1948,19 +1390,41 @@ class Engine:
         if frame.shape != want or frame.dtype != np.uint8:
             raise ValueError(f"frame must be uint8 {want}, got {frame.dtype} {frame.shape}")
         self._upload_seeds(self._check_seeds(seeds))
-        _, hin, _hout, e0, e1 = self._staging()
+        hin = self._staging()[1]
         hin.numpy()[...] = frame.reshape(hin.shape)
         self.ops.upload(self.frame_u8, hin)
+        self._launch_timed(overlap)
+
+    def _launch_timed(self, overlap: Optional[bool]):
+        """`launch` between the two events of this engine's staging: `last_gpu_ms` is the program alone, without the copies around it"""
+        e0, e1 = self._staging()[3:]
         if e0 is not None:
             e0.record(self.ops.stream)
         self.launch(overlap)
         if e1 is not None:
             e1.record(self.ops.stream)
 
+    def _raw_frames(self, frame, kind, size_of):
+        """`frame` of a raw submit -> [(frame, (left, top, right, bottom))] for the B frames of a launch: one `kind` object (B = 1) or a
+        sequence of B; size_of(f) -> (width, height), or ValueError for what is no frame; the reference's crop box, refused when empty"""
+        p = self.plan
+        H, W, B = p["H"], p["W"], p["batch"]
+        frames = [frame] if B == 1 and isinstance(frame, kind) else list(frame)
+        if len(frames) != B:
+            raise ValueError(f"this engine takes {B} frame(s) per launch, got {len(frames)}")
+        out = []
+        for f in frames:
+            w, h = size_of(f)
+            l, t, r, b = self.ops.center_crop_box(w, h, W, H)
+            if not (0 <= l < r <= w and 0 <= t < b <= h):
+                raise ValueError(f"the crop box of a {w} x {h} frame for {W} x {H} is empty")
+            out.append((f, (l, t, r, b)))
+        return out
+
     def _raw_staging(self, nbytes: int):
         """Pinned host bytes and device bytes for the crop boxes of camera frames (`submit_raw_u8`); grown, never shrunk.  The lane's
         previous launch has been collected (= its stream waited for) before the next submit, so nothing in flight reads the old ones."""
-        st = getattr(self, "_raw_stage", None)
+        st = self._raw_stage
         if st is None or st[0].numel() < nbytes:
             n = _ru(max(nbytes, 1 << 20), 1 << 20)
             st = (torch.empty(n, dtype=torch.uint8, pin_memory=torch.cuda.is_available()), self.ops.empty(n, dtype=torch.uint8))
@@ -1975,22 +1439,19 @@ class Engine:
         p = self.plan
         seeds = self._check_seeds(seeds)
         H, W, B = p["H"], p["W"], p["batch"]
-        frames = [frame] if B == 1 and isinstance(frame, np.ndarray) else list(frame)
-        if len(frames) != B:
-            raise ValueError(f"this engine takes {B} frame(s) per launch, got {len(frames)}")
-        boxes, total = [], 0
-        for f in frames:
+
+        def size_of(f):
             if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 or f.shape[0] < 1 or f.shape[1] < 1:
                 raise ValueError(f"frame must be uint8 [h][w][3], got {getattr(f, 'dtype', type(f))} {getattr(f, 'shape', '')}")
-            l, t, r, b = self.ops.center_crop_box(f.shape[1], f.shape[0], W, H)
-            if not (0 <= l < r <= f.shape[1] and 0 <= t < b <= f.shape[0]):
-                raise ValueError(f"the crop box of a {f.shape[1]} x {f.shape[0]} frame for {W} x {H} is empty")
-            boxes.append((l, t, r, b, total))
+            return f.shape[1], f.shape[0]
+
+        boxes, total = [], 0
+        for f, (l, t, r, b) in self._raw_frames(frame, np.ndarray, size_of):
+            boxes.append((f, (l, t, r, b, total)))
             total += _ru((r - l) * (b - t) * 3, 256)
         hraw, draw = self._raw_staging(total)
-        _, _hin, _hout, e0, e1 = self._staging()
         self._upload_seeds(seeds)
-        for i, (f, (l, t, r, b, off)) in enumerate(zip(frames, boxes)):
+        for i, (f, (l, t, r, b, off)) in enumerate(boxes):
             bw, bh = r - l, b - t
             n = bw * bh * 3
             hraw.numpy()[off:off + n].reshape(bh, bw, 3)[...] = f[t:b, l:r]  # (only the crop box travels)
@@ -2000,11 +1461,7 @@ class Engine:
             else:
                 self.ops.upload(draw[off:off + n], hraw[off:off + n])
                 self.ops.resample_rgb(draw[off:off + n], bh, bw, bw * 3, (0, 0, bw, bh), dst, H, W)
-        if e0 is not None:
-            e0.record(self.ops.stream)
-        self.launch(overlap)
-        if e1 is not None:
-            e1.record(self.ops.stream)
+        self._launch_timed(overlap)
 
     def infer_raw_u8(self, frame) -> np.ndarray:
         """camera frame(s) of any size -> uint8 [H][W][3] ([B][H][W][3]): `infer_u8` of the centre-cropped, LANCZOS-resized frame(s)"""
@@ -2023,30 +1480,27 @@ class Engine:
         p = self.plan
         seeds = self._check_seeds(seeds)
         H, W, B = p["H"], p["W"], p["batch"]
-        frames = [frame] if B == 1 and isinstance(frame, I420Frame) else list(frame)
-        if len(frames) != B:
-            raise ValueError(f"this engine takes {B} frame(s) per launch, got {len(frames)}")
-        rects, total, scratch = [], 0, 0
-        for f in frames:
+
+        def size_of(f):
             if not isinstance(f, I420Frame):
                 raise ValueError(f"frame must be an I420Frame, got {type(f).__name__}")
-            l, t, r, b = self.ops.center_crop_box(f.width, f.height, W, H)
-            if not (0 <= l < r <= f.width and 0 <= t < b <= f.height):
-                raise ValueError(f"the crop box of a {f.width} x {f.height} frame for {W} x {H} is empty")
+            return f.width, f.height
+
+        rects, total, scratch = [], 0, 0
+        for f, (l, t, r, b) in self._raw_frames(frame, I420Frame, size_of):
             el, et = l & ~1, t & ~1
             rw, rh = r - el, b - et
             cw, ch = (rw + 1) // 2, (rh + 1) // 2
             ys, cs = _ru(rw, 4), _ru(cw, 4)  # (device rows start on a dword: the conversion's dword-wide form)
-            rects.append((l, t, r, b, el, et, rw, rh, cw, ch, ys, cs, total))
+            rects.append((f, (l, t, r, b, el, et, rw, rh, cw, ch, ys, cs, total)))
             total += _ru(ys * rh + 2 * cs * ch, 256)
             if not ((r - l, b - t) == (W, H) and (el, et) == (l, t)):
                 scratch = max(scratch, _ru(rw * 3, 4) * rh)
         hraw, draw = self._raw_staging(total)
         rgb = self.ops.workspace("i420_rgb", scratch) if scratch else None
-        _, _hin, _hout, e0, e1 = self._staging()
         self._upload_seeds(seeds)
         hb = hraw.numpy()
-        for i, (f, (l, t, r, b, el, et, rw, rh, cw, ch, ys, cs, off)) in enumerate(zip(frames, rects)):
+        for i, (f, (l, t, r, b, el, et, rw, rh, cw, ch, ys, cs, off)) in enumerate(rects):
             ou, ov = off + ys * rh, off + ys * rh + cs * ch
             hb[off:ou].reshape(rh, ys)[:, :rw] = f.y[et:b, el:r]  # (only the crop box's plane rectangles travel)
             hb[ou:ov].reshape(ch, cs)[:, :cw] = f.u[et // 2:et // 2 + ch, el // 2:el // 2 + cw]
@@ -2062,11 +1516,7 @@ class Engine:
                 self.ops.i420_to_rgb(dy, ys, du, dv, cs, 0, 0, rh, rw, rgb, row)
                 self.ops.resample_rgb(rgb, rh, rw, row, (l - el, t - et, r - el, b - et), dst, H, W)
         self.last_upload_bytes = total  # (counted: what `upload` was handed; VideoSDPipeline.metrics reports it per frame)
-        if e0 is not None:
-            e0.record(self.ops.stream)
-        self.launch(overlap)
-        if e1 is not None:
-            e1.record(self.ops.stream)
+        self._launch_timed(overlap)
         self._enqueue_i420()  # (behind the captured program at submit, as vsd_plan_submit_frame_i420 does: nothing is launched at collect)
 
     def _enqueue_i420(self):
@@ -2076,7 +1526,7 @@ class Engine:
         if (H | W) & 1:
             raise ValueError(f"I420 output: a {W} x {H} frame has an odd side")
         one = H * W * 3 // 2
-        st = getattr(self, "_i420_stage", None)
+        st = self._i420_stage
         if st is None or st[0].numel() != B * one:
             st = (self.ops.empty(B * one, dtype=torch.uint8), torch.empty(B * one, dtype=torch.uint8, pin_memory=torch.cuda.is_available()))
             self._i420_stage = st
@@ -2095,7 +1545,7 @@ class Engine:
 
         p = self.plan
         H, W, B = p["H"], p["W"], p["batch"]
-        if not getattr(self, "_i420_queued", False):
+        if not self._i420_queued:
             self._enqueue_i420()
         self._i420_queued = False
         dev, host = self._i420_stage

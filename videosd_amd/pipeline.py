@@ -283,7 +283,7 @@ class VideoSDPipeline:
     def _prompts_in_use(self):
         """ids of the cache entries a submitted, not yet collected launch of a `frame_prompts` engine reads from (its installs may not have
         executed yet) -- the LRU never drops those"""
-        return {id(b) for e in self._outstanding for b in getattr(e, "_slot_src", ()) if b is not None}
+        return {id(b) for e in self._outstanding for b in (e._prompt_slots.src if e._prompt_slots is not None else ()) if b is not None}
 
     def _cache_prompt(self, key, embeds=None, prompt=None, keep=()):
         blk = self._prompts.get(key)
@@ -529,7 +529,7 @@ class VideoSDPipeline:
         eng.use_prompts(pblock) if plist is not None else eng.use_prompt(pblock)
         if frame_opts:  # (a changed frame slot is rewritten on this lane's stream ahead of the program: nobody waits)
             eng.use_options(list(zip(strengths, cn_scales)))
-        if use_ref and getattr(eng, "_ref_epoch", None) != self._ref_epoch:
+        if use_ref and eng._ref_epoch != self._ref_epoch:
             rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), width, height), dtype=np.uint8)
             eng.ops.upload(eng.ref_u8, torch.from_numpy(np.array(rf, copy=True)))  # (PIL's buffer is read-only)
             eng._ref_epoch = self._ref_epoch
@@ -611,7 +611,7 @@ class VideoSDPipeline:
                 self._lanes_busy.pop(i)
         self._note("wait_download", t0)
         self._io_bytes["down"] = (eng.last_download_bytes if on_device else out.nbytes) // n
-        if getattr(eng, "last_gpu_ms", None) is not None:
+        if eng.last_gpu_ms is not None:
             self._host_ms["gpu"].append(eng.last_gpu_ms)
         if on_device:
             t0 = time.perf_counter()
@@ -721,7 +721,6 @@ class VideoSDPipeline:
             mode["frame_options"] = True
         eng.prepare(height, width, steps, strength, controlnet_scale=cn_scale, use_controlnet=use_cn, batch=batch, ref_mode=use_ref,
                     autotune=self.tuning_mode != "table", **mode)
-        eng._ref_epoch = None
         plan["engines"][(batch, lane)] = eng
         self._note("prepare", t0)
         return eng

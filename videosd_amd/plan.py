@@ -179,6 +179,7 @@ def option_coefficients(nres: int) -> torch.Tensor:
     """fp32 [50][6] per timestep 19, 39, ... 999 -- sqrt(a_t), sqrt(1 - a_t), c_skip, c_out, the two add-noise values, by
     lcm.LCMSchedule.step_coef / add_noise_coef themselves -- followed by logspace(-1, 0, nres): what vsd_plan_set_options builds the
     constant block of any schedule from (step i takes columns 0..3 of its timestep's row and columns 0..1 of the next step's)"""
+    from .blocks import controlnet_scales
     from .lcm import LCMSchedule, lcm_timesteps
 
     sched = LCMSchedule(1.0, 1)
@@ -186,7 +187,7 @@ def option_coefficients(nres: int) -> torch.Tensor:
     for t in sorted(lcm_timesteps(1.0, OPT_ROWS)):
         sched.timesteps = [t]
         rows.append(list(sched.step_coef(0)[:4]) + list(sched.add_noise_coef()))
-    return torch.cat([torch.tensor(rows, dtype=torch.float32).reshape(-1), torch.logspace(-1, 0, nres)])
+    return torch.cat([torch.tensor(rows, dtype=torch.float32).reshape(-1), controlnet_scales(nres, 1.0)])
 
 
 def _option_tables(engine):
@@ -199,7 +200,7 @@ def _option_tables(engine):
     every = sorted(lcm_timesteps(1.0, OPT_ROWS))  # 19, 39, ... 999: row j holds timestep 20 j + 19
     assert len(every) == OPT_ROWS and all(t == 20 * j + 19 for j, t in enumerate(every))
     sched = LCMSchedule(1.0, 1)
-    nets = [("unet", engine.unet, True)] + ([("cn", engine.cn, True)] if p["cn"] and engine.cn is not None else [])
+    nets = [(name, net, True) for name, net in engine._networks(p["cn"])]
     if engine.shared.get("ref_mode"):
         nets.append(("ref", engine.unet, False))
     tables = []
@@ -214,7 +215,7 @@ def _option_tables(engine):
             with torch.cuda.stream(ops.stream):
                 table[r0:r0 + len(ts)].copy_(chunk[:len(ts)])
         tables.append((name, live, table))
-    nres = 13 if engine.cn is None else len(engine.cn.zero_convs) + 1
+    nres = engine._nres()
     coef_dev = ops.to_device(option_coefficients(nres))
     ops.synchronize()
     return tables, coef_dev, nres
@@ -326,8 +327,8 @@ def export_plan(engine, path: str) -> dict:
     assert len(opts) == OPT_FIXED_BYTES + OPT_TABLE_BYTES * len(tables)
     ext = struct.pack("<IQ", L.VERSION, signature_hash()) + opts
     # what may be shared between lanes: allocations that hold a network's weight tensor -- and are nothing the program writes
-    private = [engine.pblock.buf, consts, coef_dev, engine.noise, getattr(engine, "seed_dev", None), engine.frame_u8, engine.out_u8, engine.edge_u8, getattr(engine, "noise_ref", None),
-               getattr(engine, "ref_u8", None)] + [t for _, live, table in tables for t in (live, table)] + list(engine.shared["temb"].values())
+    private = [engine.pblock.buf, consts, coef_dev, engine.noise, engine.seed_dev, engine.frame_u8, engine.out_u8, engine.edge_u8, engine.noise_ref,
+               engine.ref_u8] + [t for _, live, table in tables for t in (live, table)] + list(engine.shared["temb"].values())
     never = {regs.find(t.untyped_storage().data_ptr()) for t in private if t is not None} | {regs.find(s) for s in scratch}
     seen = set()
     weights = {regs.find(t.untyped_storage().data_ptr()) for net in (engine.unet, engine.cn, engine.vae) for t in _weight_tensors(net, seen) if t.is_cuda}
