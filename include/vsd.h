@@ -72,7 +72,8 @@ const char* vsd_last_error(vsd_ctx* ctx);
  * ResnetBlock2D, Transformer2DModel, Downsample2D, Upsample2D, Attention and FeedForward under
  * lcm_controlnet.py:558 (ControlNet), :568 (UNet), :299/:594 (TAESD).
  * epilogue: v = acc + bias[n] + rowvec[n]; v = act(v); v *= out_scale; v += residual + residual2;
- *           [act | VSD_ACT_POST: the activation is applied here instead]  out = v;  out2 = v + add2.
+ *           [act | VSD_ACT_POST: the activation is applied here instead]  out = fp16(v), the one rounding;  out2 = fp16(out + add2),
+ *           of the STORED out.
  * act == GEGLU: weights/bias are tile-packed (64 hidden + 64 gate rows per 128-row tile); the output
  * has n/2 columns: out[m][j] = (h_j + b) * gelu_erf(g_j + b).
  * Columns >= t_col0 (when out_t != NULL) are written TRANSPOSED to out_t[(n - t_col0) * ldt + m]

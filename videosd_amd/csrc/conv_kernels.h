@@ -265,8 +265,11 @@ __device__ __forceinline__ void epilogue_store8(const ConvParams& p, int m, int 
       float x = p.residual ? __builtin_fmaf(v[i], sc, (float)p.residual[(size_t)m * p.ldr + n + i]) : v[i] * sc;
       if (p.residual2) x += (float)p.residual2[(size_t)m * p.ldr + n + i];
       if (post) x = apply_act(x);
-      p.out[(size_t)m * p.ldo + n + i] = (half_t)x;
-      if (p.out2) p.out2[(size_t)m * p.ldo + n + i] = (half_t)(x + (float)p.add2[(size_t)m * p.ldo + n + i]);
+      const half_t o = (half_t)x;
+      p.out[(size_t)m * p.ldo + n + i] = o;
+      // (out2 = out + add2 of the STORED out, as the 8-wide form above: adding to the unrounded x gave the last N % 8 columns of a
+      //  tensor other bits than the rest wherever |x| passes 2048 -- tests/test_exact_gpu.py, case epi-out2-n196)
+      if (p.out2) p.out2[(size_t)m * p.ldo + n + i] = (half_t)((float)o + (float)p.add2[(size_t)m * p.ldo + n + i]);
     }
   }
 }
