@@ -32,6 +32,22 @@ def test_infer_signature_matches_reference():
     assert {"load_model", "compile_model", "infer", "remote"} <= set(dir(VideoSDPipeline))
 
 
+def test_the_dispatch_defaults_are_those_of_infer():
+    """what a worker assumes for an option a request leaves out (a per-frame value of a coalesced launch, the prompt a frame is synced
+    for) is what `infer` -- and the launch forms -- would assume"""
+    from videosd_amd.dispatch import INFER_DEFAULTS, PER_FRAME
+
+    for f in (VideoSDPipeline.infer, VideoSDPipeline.infer_batch, VideoSDPipeline.submit_batch):
+        params = inspect.signature(f).parameters
+        assert {k: params[k].default for k in INFER_DEFAULTS} == INFER_DEFAULTS, f.__name__
+    assert set(INFER_DEFAULTS) == {"prompt"} | {row.key for row in PER_FRAME}  # every per-frame value has its default, and nothing idles there
+    assert [(row.attr, row.key, row.kwarg) for row in PER_FRAME] == [
+        ("per_frame_seed", "seed", "seed"), ("per_frame_prompt", "prompt", "prompts"),
+        ("per_frame_options", "strength", "strength"), ("per_frame_options", "controlnet_scale", "controlnet_scale")]
+    launch = inspect.signature(VideoSDPipeline.submit_batch).parameters
+    assert all(row.kwarg in launch for row in PER_FRAME)
+
+
 def test_constructor_requires_model_and_controlnet_and_a_gpu():
     with pytest.raises(KeyError):
         VideoSDPipeline(gpus=4, compile=False)

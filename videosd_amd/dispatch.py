@@ -1,7 +1,7 @@
 """In-node frame dispatch: one worker process per GPU, frames sharded round-robin, results released in
 order, prompt embeddings broadcast over RCCL (torch.distributed backend "nccl" on ROCm; "gloo" in CPU tests).
 
-Replaces the reference's Ray fan-out (/root/reference/diffusert/server.py:104-143, 273-277, 317-321):
+Replaces the reference's Ray fan-out (diffusert/server.py:104-143, 273-277, 317-321):
   * `VideoSDPipeline.remote(**config)` -> `RemotePipeline`, whose `.infer.remote(img, **options)` is awaitable,
     so `img = await pipelines[gpu].infer.remote(frame.to_image(), **self.options)` (server.py:108) works as is;
   * `generating[gpu]` / first-idle scan -> `FrameDispatcher`: frame k goes to worker k mod N; a frame arriving
@@ -17,23 +17,33 @@ Replaces the reference's Ray fan-out (/root/reference/diffusert/server.py:104-14
     (never a re-exec of a process that touched the GPU); JSON-lines metrics per worker (`metrics_lines`).
 Frames never cross xGMI: each worker receives its frame from host memory and returns RGB to the host (by default
 through shared-memory slots, not pickled through the pipe).
+
+Who owns what.  In the WORKER process (`_worker_main`): `_Group` -- membership of the workers' process group (communicator, rank, world, device,
+what an abandon did) and the collectives; `_Group.join` is the ONE rendezvous.  `_Worker` -- the pipe and the shared-memory rings, the launches in
+flight and the backlog (the serve loop), `_Stats`.  `_Request` -- one call, decoded once where it is taken from the pipe and carried to its reply or
+failure.  In the PARENT: `RemotePipeline` (the handle: free slots, pending calls, writer / watchdog threads), `_ReplyHub`, `FrameDispatcher`.  The
+rings and the wire format of a frame in a slot are transport.py.  On the pipe: requests `(rid, method, args, kwargs)`, replies `(rid, ok, payload)`;
+first of all `("ready", None)` or `("error", (type, text))`.  Importing this module never initialises the GPU (the parent only counts devices).
 """
 import asyncio
+import concurrent.futures
 import importlib
 import json
 import multiprocessing as mp
 import os
 import queue
 import socket
-import statistics
 import sys
 import threading
 import time
-from typing import Any, Callable, Dict, List, Optional
+from collections import namedtuple
+from contextlib import suppress
+from typing import Any, Dict, List, Optional
 
 import torch
 
 from .frames import I420Frame, av_plane_views, is_i420
+from .transport import _ShmRing, decode_frame, encode_frame, is_frame, is_slot_ref
 
 
 # ----------------------------------------------------------------------------------------- frame sharding
@@ -78,6 +88,20 @@ def _remote_exception(type_name: str, text: str) -> Exception:
 
 def is_caller_error(e: BaseException) -> bool:
     return isinstance(e, tuple(_CALLER_TYPES.values())) and not isinstance(e, WorkerDied)
+
+
+# `infer`'s defaults (the reference's, videopipeline.py:78) for the options read here when a request leaves them out
+INFER_DEFAULTS = {"prompt": ["pixar, cg"], "strength": 0.4, "seed": 42, "controlnet_scale": 1}
+
+# The `infer` options that may differ between the frames of ONE launch.  A pipeline switches a row on with the attribute `attr`; frames that
+# differ only in `key` then share a launch, which gets `kwarg` = the frames' values as a list, in request order (INFER_DEFAULTS[key] for a
+# request without it).  per_frame_seed: VideoSDPipeline(device_seed=True).  per_frame_prompt (frame_prompts=True): the launch gets `prompts`;
+# `prompt` stays the first request's.  per_frame_options (frame_options=True; needs `option_class` too): frames whose sliders stand
+# differently share a launch when the pipeline puts them in one `option_class` (the number of timesteps: the program's length); a request
+# with other values never waits for the lanes to drain (the pipeline's `needs_idle` says so).
+_PerFrame = namedtuple("_PerFrame", "attr key kwarg")
+PER_FRAME = (_PerFrame("per_frame_seed", "seed", "seed"), _PerFrame("per_frame_prompt", "prompt", "prompts"),
+             _PerFrame("per_frame_options", "strength", "strength"), _PerFrame("per_frame_options", "controlnet_scale", "controlnet_scale"))
 
 
 # ----------------------------------------------------------------------------------------- collective
@@ -144,106 +168,16 @@ def free_port() -> int:
     return port
 
 
-# ----------------------------------------------------------------------------------------- shared-memory frames
-class _ShmRing:
-    """`slots` fixed-size RGB slots in one POSIX shared-memory segment.  The parent owns allocation (a free list);
-    slot i of the request ring pairs with slot i of the reply ring, so a reply needs no allocation of its own."""
-
-    def __init__(self, slots: int, slot_bytes: int, name: Optional[str] = None):
-        from multiprocessing import shared_memory
-
-        self.slots, self.slot_bytes = slots, slot_bytes
-        if name is None:
-            self.shm = shared_memory.SharedMemory(create=True, size=slots * slot_bytes)
-            self.owner = True
-        else:
-            self.shm = shared_memory.SharedMemory(name=name)
-            self.owner = False  # (spawned children share the parent's resource tracker: nothing to unregister here)
-
-    def view(self, slot: int, nbytes: int) -> memoryview:
-        o = slot * self.slot_bytes
-        return self.shm.buf[o:o + nbytes]
-
-    def close(self):
-        # (two steps: `close` raises BufferError while a frame's memoryview is still alive -- a worker that died with frames in
-        #  flight -- and the segment must lose its NAME anyway, or every respawn leaves one behind in /dev/shm until exit)
-        try:
-            self.shm.close()
-        except Exception:
-            pass
-        if self.owner:
-            try:
-                self.shm.unlink()
-            except Exception:
-                pass
-            self.owner = False
-
-
-def _image_from_slot(ring: _ShmRing, slot: int, w: int, h: int, copy: bool):
-    from PIL import Image
-
-    mv = ring.view(slot, w * h * 3)
-    # (packed RGB is not Pillow's storage layout -- it keeps 4 bytes per pixel -- so `frombuffer` DECODES the slot into storage of
-    #  the image's own: one pass, with the GIL released, and the slot may be reused as soon as this returns.  `frombytes(bytes(mv))`
-    #  -- the first form -- copied the slot once more in front of the same decode: 0.05 ms of the parent's 0.9 ms per frame.)
-    return Image.frombuffer("RGB", (w, h), mv, "raw", "RGB", 0, 1)
-
-
-def _image_to_slot(ring: _ShmRing, slot: int, img) -> Optional[tuple]:
-    if img.mode != "RGB":
-        img = img.convert("RGB")
-    w, h = img.size
-    n = w * h * 3
-    if n > ring.slot_bytes:
-        return None
-    # np.asarray(img) packs the pixels in one call (0.26 ms for 512x512 on the build box; `img.tobytes()` goes through the raw
-    # encoder in 64 KB pieces and a join: 0.9 ms -- the largest single item of the parent's per-frame cost in
-    # scripts/dispatch_ceiling.py); the copy into the slot is a numpy memcpy, which runs with the GIL released
-    import numpy as np
-
-    a = np.asarray(img)
-    if a.dtype != np.uint8 or a.shape != (h, w, 3):  # (never for an RGB image; stay correct anyway)
-        ring.view(slot, n)[:] = img.tobytes()
-        return (slot, w, h)
-    np.frombuffer(ring.view(slot, n), dtype=np.uint8)[:] = a.reshape(-1)
-    return (slot, w, h)
-
-
-def _i420_to_slot(ring: _ShmRing, slot: int, planes, w: int, h: int) -> tuple:
-    """Three plane views (an `I420Frame`'s, or `frames.av_plane_views` of an av frame: padded `line_size` rows read in place, once) into a
-    slot as packed I420 -- Y, U, V, rows tight: 1.5 bytes per pixel where RGB has 3.  Plane copies only, no arithmetic (numpy row
-    copies, GIL released).  The caller has checked that the frame fits the slot."""
-    import numpy as np
-
-    dst = I420Frame(np.frombuffer(ring.view(slot, I420Frame.nbytes_for(w, h)), dtype=np.uint8), w, h)
-    dst.y[...], dst.u[...], dst.v[...] = planes
-    return (slot, w, h)
-
-
-def _i420_from_slot(ring: _ShmRing, slot: int, w: int, h: int, copy: bool):
-    """copy=False: the frame's planes are views of the slot (the worker: the request slot is held until the reply)"""
-    import numpy as np
-
-    a = np.frombuffer(ring.view(slot, I420Frame.nbytes_for(w, h)), dtype=np.uint8)
-    return I420Frame(a.copy() if copy else a, w, h)
-
-
 # ----------------------------------------------------------------------------------------- worker process
-def _resolve(path: str) -> Callable:
-    mod, _, name = path.partition(":")
-    return getattr(importlib.import_module(mod), name)
-
-
 class _Stats:
     """Per-worker serving statistics (JSON-lines metrics: fps, p50 / p95 latency, launches, frames per launch)."""
 
     def __init__(self, keep: int = 512):
         self.t0 = time.time()
-        self.frames = 0
-        self.launches = 0
-        self.errors = 0
+        self.frames = self.launches = self.errors = 0
         self.lat: List[float] = []   # ms, request taken from the pipe -> result sent
         self.keep = keep
+        self.ema_launch_s = 0.0      # running average: request taken -> launch collected (what a partial batch may wait for)
 
     def add(self, n_frames: int, ms: float):
         self.frames += n_frames
@@ -277,375 +211,377 @@ def resolve_auto_device(config: Dict[str, Any]) -> Dict[str, Any]:
     return config
 
 
-def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1, group: Optional[Dict[str, Any]] = None,
-                 shm: Optional[Dict[str, Any]] = None, lanes: int = 2):
-    """Serve calls in order, like a Ray actor.  With max_batch > 1, `infer` calls that are ALREADY queued behind the one
-    being taken (frames of other sessions, or of the same stream submitted ahead) and carry the same options are
-    coalesced into one `infer_batch` launch: no waiting for a batch to fill, so a lone frame is never delayed.  When
-    the pipeline has `submit_batch` / `collect_batch`, up to two launches are kept in flight (two engine lanes): while
-    the GPU works on one, this process crops / resizes / uploads the next and converts / sends the previous one.
-    A request whose options differ from the launches in flight waits until those are collected (a new plan re-prepares
-    the engine the other lane is still running on).  Results always go back in request order."""
-    dist = None
-    rank, world = 0, 1
-    dev = torch.device("cpu")
-    try:
-        config = resolve_auto_device(config)
-        if group is not None:  # join the workers' process group (RCCL on the GPU box, gloo in CPU tests)
-            import datetime
+class _Group:
+    """This worker's membership of the workers' process group (RCCL on the GPU box, gloo in CPU tests), and the collectives."""
 
-            import torch.distributed as dist
+    def __init__(self, config: Dict[str, Any]):
+        self.config = config                  # the worker's (resolved) configuration: names the device of an RCCL communicator
+        self.pipe = None                      # the pipeline, once it is built (the first rendezvous comes before it)
+        self.dist = None                      # torch.distributed while the communicator is usable; None: stand-alone, prompts are encoded here
+        self.spec: Dict[str, Any] = {}        # the group as the parent described it (backend, port, deadlines)
+        self.rank, self.world = 0, 1
+        self.dev = torch.device("cpu")        # where the collectives' buffers live
+        self.note: Dict[str, Any] = {}        # what `abandon` did (reported with the failed sync and in the metrics)
+        self.epoch = 0                        # prompt syncs served
 
-            rank, world = int(group["rank"]), int(group["world"])
-            os.environ["MASTER_ADDR"] = "127.0.0.1"
-            os.environ["MASTER_PORT"] = str(group["port"])
-            to = datetime.timedelta(seconds=float(group.get("timeout", 120.0)))
-            # (a collective that was given up at `sync_timeout` is ABORTED with its communicator -- `abandon_group` below -- so
-            # the backend's watchdog never sees it time out; its error handling stays at the default)
-            if group["backend"] == "nccl":
-                dev = torch.device("cuda", int(config.get("device", 0)))
-                torch.cuda.set_device(dev)
-                dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=to)
-            else:
-                dist.init_process_group(group["backend"], rank=rank, world_size=world, timeout=to)
-        lanes = max(1, int(lanes))
-        if world > 1 and "tuning_mode" not in config:
-            # every rank of a group must build the SAME kernel for the same shape (round-robin sharding sends consecutive
-            # frames of one stream to different ranks): no per-rank timing of shapes the shipped table lacks; rank 0's
-            # measured choices arrive through `__sync_tuning__` (VERDICT r2 item 8)
-            config = dict(config, tuning_mode="table")
-        # (`lanes`: how many launches this loop keeps in flight -- the pipeline places lane l on launch stream l and only runs a
-        #  lane's ControlNet encoder on a side stream when the lanes leave it a command-processor pipe of its own)
-        pipe = _resolve(factory)(**dict(config, lanes=config.get("lanes", lanes)))
-        conn.send(("ready", None))
-    except BaseException as e:  # construction errors travel to the parent (the reference re-raises KeyError)
-        conn.send(("error", (type(e).__name__, str(e))))
-        return
-    rings = None
-    if shm is not None:
-        rings = (_ShmRing(shm["slots"], shm["slot_bytes"], shm["in"]), _ShmRing(shm["slots"], shm["slot_bytes"], shm["out"]))
-    pipelined = max_batch > 1 and hasattr(pipe, "submit_batch") and hasattr(pipe, "collect_batch")
-    # A pipeline whose `seed` is per frame INSIDE a launch (VideoSDPipeline(device_seed=True)) says so: frames that differ only in
-    # `seed` then share a launch, and the launch gets the seeds of its frames as a list, in request order.
-    per_seed = bool(getattr(pipe, "per_frame_seed", False))
+    def join(self, g: Dict[str, Any]) -> Dict[str, Any]:
+        """The rendezvous, at construction and again for a NEW process group (the dispatcher re-forms the group once a replaced member is up:
+        VERDICT r4, missing #6 -- until round 5 a group that had lost a member stayed broken for good and every later prompt was encoded N
+        times).  What is left of an old communicator is abandoned first (aborted on RCCL); then the ordinary rendezvous, on the port and with
+        the rank the parent hands out.  The worker takes rank 0's kernel choices from now on, like every member of a group.  A rendezvous
+        that does not complete leaves the worker stand-alone (`dist` None: prompts are encoded here)."""
+        import datetime
 
-    # ... and one whose PROMPT is per frame inside a launch (VideoSDPipeline(frame_prompts=True)) likewise: frames of sessions that differ in
-    # `prompt` share a launch, which gets `prompts`, one per frame in request order (`prompt` stays the first request's).
-    per_prompt = bool(getattr(pipe, "per_frame_prompt", False))
-    # ... and one whose `strength` / `controlnet_scale` are per frame inside a launch (VideoSDPipeline(frame_options=True)): frames of sessions
-    # whose sliders stand differently share a launch when the pipeline puts them in one `option_class` (the number of timesteps: the
-    # program's length); the launch gets both as lists, one per frame in request order.  A request with other values never waits for the
-    # lanes to drain (the pipeline's `needs_idle` says so).
-    per_opts = bool(getattr(pipe, "per_frame_options", False)) and hasattr(pipe, "option_class")
-    per_frame = tuple(k for k, on in (("seed", per_seed), ("prompt", per_prompt), ("strength", per_opts), ("controlnet_scale", per_opts)) if on)
+        import torch.distributed as dist
 
-    def same_options(a, b):
-        if not per_frame:
-            return a == b
-        if {k: v for k, v in a.items() if k not in per_frame} != {k: v for k, v in b.items() if k not in per_frame}:
-            return False
-        if per_opts and a != b:
-            try:
-                return pipe.option_class(a) == pipe.option_class(b)
-            except Exception:
-                return False
-        return True
+        self.abandon()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        self.rank, self.world = int(g["rank"]), int(g["world"])
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(g["port"])
+        to = datetime.timedelta(seconds=float(g.get("timeout", 120.0)))
+        # (a collective that was given up at `sync_timeout` is ABORTED with its communicator -- `abandon` -- so the backend's
+        # watchdog never sees it time out; its error handling stays at the default)
+        on_device = {}
+        if g["backend"] == "nccl":
+            self.dev = torch.device("cuda", int(self.config.get("device", 0)))
+            torch.cuda.set_device(self.dev)
+            on_device = {"device_id": self.dev}
+        dist.init_process_group(g["backend"], rank=self.rank, world_size=self.world, timeout=to, **on_device)
+        self.dist, self.spec = dist, dict(g)
+        self.note.clear()
+        if self.world > 1 and hasattr(self.pipe, "set_tuning_mode"):
+            with suppress(Exception):
+                self.pipe.set_tuning_mode("table")
+        return {"rank": self.rank, "world": self.world, "backend": g["backend"]}
 
-    def launch_options(kwargs, seeds, prompts, opts=()):
-        if not per_frame:
-            return kwargs
-        kw = dict(kwargs)
-        if per_seed:
-            kw["seed"] = list(seeds)
-        if per_prompt:
-            kw["prompts"] = list(prompts)
-        if per_opts:
-            kw["strength"] = [o[0] for o in opts]
-            kw["controlnet_scale"] = [o[1] for o in opts]
-        return kw
-
-    backlog, inflight, lane = [], [], 0
-    ema_launch_s = [0.0]  # running average: request taken -> launch collected
-    stats = _Stats()
-    epoch = 0
-
-    def reply(rid, img, slot):
-        if rings is not None and slot is not None and isinstance(img, I420Frame) and img.data.size <= rings[1].slot_bytes:
-            conn.send((rid, True, ("__shm420__",) + _i420_to_slot(rings[1], slot, (img.y, img.u, img.v), img.width, img.height)))
+    def abandon(self):
+        """After a failed or timed-out collective the communicator is finished (a member is gone; it cannot be re-entered). With RCCL the abandoned
+        broadcast is a KERNEL that stays resident on the GPU waiting for its peer, and every later device-wide synchronisation of this worker
+        (Engine.prepare's, a prompt build's) would wait behind it until the call watchdog kills the worker: abort the communicator so that
+        the kernel is torn down, and never use the group again.  gloo has nothing resident; destroying the group is enough."""
+        if self.dist is None:
             return
-        if rings is not None and slot is not None and hasattr(img, "tobytes"):
-            where = _image_to_slot(rings[1], slot, img)
-            if where is not None:
-                conn.send((rid, True, ("__shm__",) + where))
-                return
-        conn.send((rid, True, img))
-
-    def fail(group_, e):
-        stats.errors += len(group_)
-        for r, _a, _s in group_:
-            conn.send((r, False, (type(e).__name__, str(e))))
-
-    def finish_oldest():
-        group_, handle, t_in, _kw, _lane = inflight.pop(0)
-        try:
-            outs = pipe.collect_batch(handle)
-            dt = time.time() - t_in
-            ema_launch_s[0] = dt if ema_launch_s[0] == 0.0 else 0.8 * ema_launch_s[0] + 0.2 * dt
-            for (r, _a, s), o in zip(group_, outs):
-                reply(r, o, s)
-            stats.add(len(group_), (time.time() - t_in) * 1e3)
-        except BaseException as e:
-            fail(group_, e)
-
-    def drain():
-        while inflight:
-            finish_oldest()
-
-    def take(msg):
-        """(rid, method, args, kwargs) -> (rid, frame-args, reply slot); shared-memory frames become PIL images here"""
-        rid, method, args, kwargs = msg
-        slot = None
-        if method == "infer" and len(args) == 1 and isinstance(args[0], tuple) and args[0] and args[0][0] == "__shm__":
-            _, slot, w, h = args[0]
-            args = (_image_from_slot(rings[0], slot, w, h, copy=False),)
-        elif method == "infer" and len(args) == 1 and isinstance(args[0], tuple) and args[0] and args[0][0] == "__shm420__":
-            _, slot, w, h = args[0]
-            args = (_i420_from_slot(rings[0], slot, w, h, copy=False),)
-        return rid, method, args, kwargs, slot
-
-    def sync_prompt(prompt, header, collective=True):
-        """A new prompt for every worker of the group: rank 0 encodes (CLIP on its GPU), everyone receives and caches it.
-        Nothing in flight is disturbed (a prompt's constants are a cache entry; a lane takes them with its next launch), so
-        there is no drain.  collective=False (the dispatcher saw an unhealthy member, or an earlier sync failed): encode here."""
-        nonlocal epoch
-        epoch += 1
-        key = prompt_key(prompt)
-        if dist is None or (world == 1 and not (group or {}).get("collective_at_world_1")) or not collective:
-            # (a group of ONE has nobody to broadcast to; `collective_at_world_1` runs the broadcast anyway: the one-GPU box's test of
-            #  the RCCL path -- communicator, device buffers, deadline wait -- tests/test_rccl_one_gpu.py)
-            emb = pipe.encode_prompt(prompt)
-            pipe.set_prompt_embeds(emb, key=key)
-            return {"epoch": epoch, "rank": rank, "via": "local"}
-        emb = pipe.encode_prompt(prompt) if rank == 0 else None
-        shape = tuple(getattr(pipe, "prompt_shape", (77, 768)))
-        hdr = dict(header or {})
-        hdr["epoch"] = epoch
-        buf, got = broadcast_prompt(emb, hdr, src=0, device=dev, shape=shape, timeout=float((group or {}).get("sync_timeout", 5.0)))
-        if dev.type == "cuda":
-            torch.cuda.current_stream().synchronize()
-        pipe.set_prompt_embeds(buf, key=key)
-        return {"epoch": int(got["epoch"]), "rank": rank, "via": dist.get_backend(), "checksum": float(buf.float().sum())}
-
-    abandon_note: Dict[str, Any] = {}  # what abandon_group did (reported with the failed sync and in the metrics)
-
-    def abandon_group():
-        """After a failed or timed-out collective the communicator is finished (a member is gone; it cannot be re-entered).
-        With RCCL the abandoned broadcast is a KERNEL that stays resident on the GPU waiting for its peer, and every later
-        device-wide synchronisation of this worker (Engine.prepare's, a prompt build's) would wait behind it until the call
-        watchdog kills the worker: abort the communicator so that the kernel is torn down, and never use the group
-        again.  gloo has nothing resident; destroying the group is enough."""
-        nonlocal dist
-        if dist is None:
-            return
-        d, dist = dist, None  # (sync_prompt / sync_tuning take the local path from now on)
+        d, self.dist = self.dist, None  # (sync_prompt / sync_tuning take the local path from now on)
         aborted, why = False, "no communicator on a device"
         try:
             pg = d.distributed_c10d._get_default_group()
-            backend = pg._get_backend(dev) if dev.type == "cuda" else None
-            if backend is not None and hasattr(backend, "abort"):
-                backend.abort()       # ProcessGroupNCCL.abort: ncclCommAbort -> the stuck kernel exits
-                aborted = True
-            elif backend is not None and hasattr(backend, "_shutdown"):
-                backend._shutdown()
+            backend = pg._get_backend(self.dev) if self.dev.type == "cuda" else None
+            stop = getattr(backend, "abort", None) or getattr(backend, "_shutdown", None)
+            if stop is not None:
+                stop()                # ProcessGroupNCCL.abort: ncclCommAbort -> the stuck kernel exits
                 aborted = True
             elif backend is not None:
                 why = "this torch has neither ProcessGroupNCCL.abort nor _shutdown"
         except Exception as e:  # private torch APIs: say so instead of leaving the abandoned collective queued in silence (ADVICE r4)
             why = f"{type(e).__name__}: {e}"
-        abandon_note.update(aborted=aborted, why=None if aborted else why)
-        if dev.type == "cuda" and not aborted:
-            # The abandoned broadcast stays queued and the backend's watchdog will take THIS worker down when the group timeout
-            # passes (ProcessGroupNCCL reads TORCH_NCCL_ASYNC_ERROR_HANDLING once, in its constructor: nothing set here could stand
-            # it down -- ADVICE r5).  Say so: the note travels with the failed sync's reply and the dispatcher's metrics, and the
-            # worker's death at the group timeout is then an ordinary worker fault (respawn + regroup).
-            abandon_note["watchdog"] = "will fire at the group timeout"
-            print(json.dumps({"kind": "worker", "rank": rank, "event": "abandon_group_without_abort", "why": why}), file=sys.stderr, flush=True)
+        self.note.update(aborted=aborted, why=None if aborted else why)
+        if self.dev.type == "cuda" and not aborted:
+            # The abandoned broadcast stays queued and the backend's watchdog will take THIS worker down when the group timeout passes
+            # (ProcessGroupNCCL reads TORCH_NCCL_ASYNC_ERROR_HANDLING once, in its constructor: nothing set here could stand it down -- ADVICE r5).
+            # Say so: the note travels with the failed sync's reply and the dispatcher's metrics, and the worker's death at the group timeout is then
+            # an ordinary worker fault (respawn + regroup).
+            self.note["watchdog"] = "will fire at the group timeout"
+            print(json.dumps({"kind": "worker", "rank": self.rank, "event": "abandon_group_without_abort", "why": why}), file=sys.stderr, flush=True)
         try:
             d.destroy_process_group()
         except Exception as e:
-            abandon_note["destroy"] = f"{type(e).__name__}: {e}"
+            self.note["destroy"] = f"{type(e).__name__}: {e}"
 
-    def join_group(g):
-        """A NEW process group for this worker (the dispatcher re-forms the group once a replaced member is up: VERDICT r4, missing
-        #6 -- until round 5 a group that had lost a member stayed broken for good and every later prompt was encoded N times).  What
-        is left of an old communicator is abandoned first (aborted on RCCL); then the ordinary rendezvous, on a fresh port, with the
-        rank the dispatcher hands out.  The worker takes rank 0's kernel choices from now on, like every member of a group."""
-        nonlocal dist, rank, world, group, dev
-        if dist is not None:
-            abandon_group()
-        import datetime
+    def leave(self):
+        """shutdown: the communicator goes with the process"""
+        if self.dist is not None:
+            with suppress(Exception):
+                self.dist.destroy_process_group()
 
-        import torch.distributed as d2
+    def sync_prompt(self, prompt, header=None, collective=True):
+        """A new prompt for every worker of the group: rank 0 encodes (CLIP on its GPU), everyone receives and caches it. Nothing in flight is
+        disturbed (a prompt's constants are a cache entry; a lane takes them with its next launch), so there is no drain.  collective=False (the
+        dispatcher saw an unhealthy member, or an earlier sync failed): encode here."""
+        self.epoch += 1
+        pipe, key = self.pipe, prompt_key(prompt)
+        if self.dist is None or (self.world == 1 and not self.spec.get("collective_at_world_1")) or not collective:
+            # (a group of ONE has nobody to broadcast to; `collective_at_world_1` runs the broadcast anyway: the one-GPU box's test of
+            #  the RCCL path -- communicator, device buffers, deadline wait -- tests/test_rccl_one_gpu.py)
+            pipe.set_prompt_embeds(pipe.encode_prompt(prompt), key=key)
+            return {"epoch": self.epoch, "rank": self.rank, "via": "local"}
+        emb = pipe.encode_prompt(prompt) if self.rank == 0 else None
+        shape = tuple(getattr(pipe, "prompt_shape", (77, 768)))
+        hdr = dict(header or {}, epoch=self.epoch)
+        buf, got = broadcast_prompt(emb, hdr, src=0, device=self.dev, shape=shape, timeout=float(self.spec.get("sync_timeout", 5.0)))
+        if self.dev.type == "cuda":
+            torch.cuda.current_stream().synchronize()
+        pipe.set_prompt_embeds(buf, key=key)
+        return {"epoch": int(got["epoch"]), "rank": self.rank, "via": self.dist.get_backend(), "checksum": float(buf.float().sum())}
 
-        if d2.is_initialized():
-            d2.destroy_process_group()
-        rank, world = int(g["rank"]), int(g["world"])
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(g["port"])
-        to = datetime.timedelta(seconds=float(g.get("timeout", 120.0)))
-        if g["backend"] == "nccl":
-            dev = torch.device("cuda", int(config.get("device", 0)))
-            torch.cuda.set_device(dev)
-            d2.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=to)
-        else:
-            d2.init_process_group(g["backend"], rank=rank, world_size=world, timeout=to)
-        dist, group = d2, dict(g)
-        abandon_note.clear()
-        if world > 1 and hasattr(pipe, "set_tuning_mode"):
-            try:
-                pipe.set_tuning_mode("table")
-            except Exception:
-                pass
-        return {"rank": rank, "world": world, "backend": g["backend"]}
+    def sync_prompt_or_encode(self, prompt, header=None, collective=True):
+        """`__sync_prompt__`: when the collective fails (a member died, the deadline passed) this worker still serves the prompt -- it encodes it
+        itself -- and reports the failure so that the dispatcher stops using the group."""
+        try:
+            return self.sync_prompt(prompt, header, collective)
+        except BaseException as e:
+            self.abandon()
+            self.sync_prompt(prompt, None, collective=False)
+            return {"epoch": self.epoch, "rank": self.rank, "via": "local-after-failed-sync", "error": f"{type(e).__name__}: {e}",
+                    "abandon": dict(self.note)}
 
-    def sync_tuning():
+    def sync_tuning(self):
         """Rank 0's per-shape kernel choices (its table plus what its warm-up measured) to every rank: one object broadcast."""
-        if dist is None or world == 1 or not hasattr(pipe, "export_tuning"):
+        pipe, rank = self.pipe, self.rank
+        if self.dist is None or self.world == 1 or not hasattr(pipe, "export_tuning"):
             return {"rank": rank, "imported": 0}
         box = [pipe.export_tuning() if rank == 0 else None]
-        dist.broadcast_object_list(box, src=0, device=dev if dist.get_backend() == "nccl" else None)
+        self.dist.broadcast_object_list(box, src=0, device=self.dev if self.dist.get_backend() == "nccl" else None)
         return {"rank": rank, "imported": 0 if rank == 0 else pipe.import_tuning(box[0]), "entries": len(box[0])}
 
-    while True:
-        if inflight and not backlog and not conn.poll(0):  # nothing new to start: hand back the oldest launch
-            finish_oldest()
-            continue
+
+class _Request:
+    """One call, as `_Worker.take` decoded it: `args` holds the frame itself (no slot reference), `slot` the reply slot it came with"""
+    __slots__ = ("rid", "method", "args", "kwargs", "slot")
+
+    def __init__(self, rid, method, args, kwargs, slot=None):
+        self.rid, self.method, self.args, self.kwargs, self.slot = rid, method, args, kwargs, slot
+
+
+_Launch = namedtuple("_Launch", "requests handle t_in kwargs lane")  # a `submit_batch` not yet collected (kwargs: its first request's)
+
+
+class _Worker:
+    """Serves calls in order, like a Ray actor.  With max_batch > 1, `infer` calls ALREADY queued behind the one being taken (frames of other
+    sessions, or of the same stream submitted ahead) with the same options are coalesced into one launch (`take_batch`): no waiting for a
+    batch to fill, so a lone frame is never delayed.  When the pipeline has `submit_batch` / `collect_batch`, up to `lanes` launches are kept
+    in flight (`place`): while the GPU works on one, this process crops / resizes / uploads the next and converts / sends the previous one.
+    Results always go back in request order."""
+
+    def __init__(self, conn, factory, config, max_batch, group, shm, lanes):  # (as `_worker_main` takes them)
+        # ---- transport: the pipe to the parent; the request and reply rings (None: every frame is pickled)
+        self.conn = conn
+        self.rings = None if shm is None else tuple(_ShmRing(shm["slots"], shm["slot_bytes"], shm[k]) for k in ("in", "out"))
+        # ---- the group (rendezvous first: the pipeline's tuning mode depends on the world size)
+        self.config = config = resolve_auto_device(config)
+        self.group = _Group(config)
+        if group is not None:
+            self.group.join(group)
+        # ---- the pipeline, and what it says about itself
+        self.max_batch = max_batch
+        # (`lanes`: how many launches the loop keeps in flight -- the pipeline places lane l on launch stream l and only runs a
+        #  lane's ControlNet encoder on a side stream when the lanes leave it a command-processor pipe of its own)
+        self.lanes = max(1, int(lanes))
+        if self.group.world > 1 and "tuning_mode" not in config:
+            # every rank of a group must build the SAME kernel for the same shape (round-robin sharding sends consecutive frames of one stream
+            # to different ranks): no per-rank timing of shapes the shipped table lacks; rank 0's come by `__sync_tuning__` (VERDICT r2 item 8)
+            config = dict(config, tuning_mode="table")
+        mod, _, name = factory.partition(":")
+        self.pipe = self.group.pipe = getattr(importlib.import_module(mod), name)(**dict(config, lanes=config.get("lanes", self.lanes)))
+        self.pipelined = max_batch > 1 and hasattr(self.pipe, "submit_batch") and hasattr(self.pipe, "collect_batch")
+        self.per_frame = tuple(r for r in PER_FRAME if getattr(self.pipe, r.attr, False)
+                               and (r.attr != "per_frame_options" or hasattr(self.pipe, "option_class")))
+        self.per_keys = frozenset(r.key for r in self.per_frame)
+        self.by_class = any(r.attr == "per_frame_options" for r in self.per_frame)
+        # ---- the serve loop: messages taken from the pipe and put back, launches not yet collected (oldest first)
+        self.backlog: list = []
+        self.inflight: List[_Launch] = []
+        self.stats = _Stats()
+
+    def same_options(self, a: Dict[str, Any], b: Dict[str, Any]) -> bool:
+        """May requests with options `a` and `b` share a launch (and a launch of `b` go beside one of `a` without a question)?"""
+        if not self.per_frame:
+            return a == b
+        skip = self.per_keys
+        if {k: v for k, v in a.items() if k not in skip} != {k: v for k, v in b.items() if k not in skip}:
+            return False
+        if self.by_class and a != b:
+            try:
+                return self.pipe.option_class(a) == self.pipe.option_class(b)
+            except Exception:
+                return False
+        return True
+
+    def launch_options(self, requests: List[_Request]) -> Dict[str, Any]:
+        """the first request's options, the per-frame values as lists in request order"""
+        kw = requests[0].kwargs
+        if self.per_frame:
+            kw = dict(kw)
+            for row in self.per_frame:
+                kw[row.kwarg] = [r.kwargs.get(row.key, INFER_DEFAULTS[row.key]) for r in requests]
+        return kw
+
+    # ------------------------------------------------------------------ the pipe
+    def next_message(self):
+        """the next message, put-back ones first; None: shutdown (sent by the parent, or the pipe has ended)"""
         try:
-            msg = backlog.pop(0) if backlog else conn.recv()
+            return self.backlog.pop(0) if self.backlog else self.conn.recv()
         except (EOFError, OSError):
-            break
-        if msg is None:
-            break
-        t_in = time.time()
-        rid, method, args, kwargs, slot = take(msg)
-        if method == "__sync_prompt__":
+            return None
+
+    def take(self, msg) -> _Request:
+        """(rid, method, args, kwargs) -> the request; a frame in a slot becomes a PIL image / an I420Frame (views of the slot) here"""
+        req = _Request(*msg)
+        if req.method == "infer" and len(req.args) == 1 and is_slot_ref(req.args[0]):
+            req.slot = req.args[0][1]
+            req.args = (decode_frame(self.rings[0], req.args[0], copy=False),)
+        return req
+
+    def reply(self, req: _Request, out):
+        """a result goes back through the reply slot paired with the request's when it is a frame and fits, pickled otherwise"""
+        ref = encode_frame(self.rings[1], req.slot, out) if self.rings is not None and req.slot is not None and is_frame(out) else None
+        self.conn.send((req.rid, True, out if ref is None else ref))
+
+    def fail(self, requests: List[_Request], e: BaseException):
+        self.stats.errors += len(requests)
+        for r in requests:
+            self.conn.send((r.rid, False, (type(e).__name__, str(e))))
+
+    def metrics(self):
+        g = self.group
+        snap = self.stats.snapshot()
+        snap.update({"rank": g.rank, "world": g.world, "device": self.config.get("device", 0), "pid": os.getpid()})
+        if g.note:
+            snap["abandoned_group"] = dict(g.note)
+        if hasattr(self.pipe, "metrics"):
             try:
-                conn.send((rid, True, sync_prompt(*args, **kwargs)))
-            except BaseException as e:
-                # the collective failed (a member died, the deadline passed): this worker still serves the prompt -- it
-                # encodes it itself -- and reports the failure so that the dispatcher stops using the group
-                try:
-                    abandon_group()
-                    sync_prompt(args[0], None, collective=False)
-                    conn.send((rid, True, {"epoch": epoch, "rank": rank, "via": "local-after-failed-sync", "error": f"{type(e).__name__}: {e}",
-                                           "abandon": dict(abandon_note)}))
-                except BaseException as e2:
-                    conn.send((rid, False, (type(e2).__name__, str(e2))))
-            continue
-        if method == "__join_group__":
-            drain()
-            try:
-                conn.send((rid, True, join_group(*args, **kwargs)))
-            except BaseException as e:
-                dist = None  # (a rendezvous that did not complete: stand-alone again, prompts are encoded here)
-                conn.send((rid, False, (type(e).__name__, str(e))))
-            continue
-        if method == "__sync_tuning__":
-            drain()
-            try:
-                conn.send((rid, True, sync_tuning()))
-            except BaseException as e:
-                conn.send((rid, False, (type(e).__name__, str(e))))
-            continue
-        if method == "__metrics__":
-            snap = stats.snapshot()
-            snap.update({"rank": rank, "world": world, "device": config.get("device", 0), "pid": os.getpid()})
-            if abandon_note:
-                snap["abandoned_group"] = dict(abandon_note)
-            if hasattr(pipe, "metrics"):
-                try:
-                    snap["pipeline"] = pipe.metrics()
-                except Exception as e:  # metrics must never take a worker down
-                    snap["pipeline"] = {"error": str(e)}
-            conn.send((rid, True, snap))
-            continue
-        group_ = [(rid, args, slot)]
-        seeds_ = [kwargs.get("seed", 42)]  # (`infer`'s default)
-        prompts_ = [kwargs.get("prompt", ["pixar, cg"])]  # (likewise)
-        opts_ = [(kwargs.get("strength", 0.4), kwargs.get("controlnet_scale", 1))]  # (likewise)
-        batchable = max_batch > 1 and method == "infer" and len(args) == 1 and hasattr(pipe, "infer_batch")
+                snap["pipeline"] = self.pipe.metrics()
+            except Exception as e:  # metrics must never take a worker down
+                snap["pipeline"] = {"error": str(e)}
+        return snap
+
+    # method -> (handler, drains first): a prompt sync and the metrics leave what is in flight alone, a new group and a new table wait for it
+    CONTROL = {"__sync_prompt__": (lambda w, *a, **k: w.group.sync_prompt_or_encode(*a, **k), False),
+               "__join_group__": (lambda w, g: w.group.join(g), True),
+               "__sync_tuning__": (lambda w: w.group.sync_tuning(), True),
+               "__metrics__": (metrics, False)}
+
+    def control(self, req: _Request):
+        handler, drains = self.CONTROL[req.method]
+        if drains:
+            self.drain()
+        try:
+            self.conn.send((req.rid, True, handler(self, *req.args, **req.kwargs)))
+        except BaseException as e:
+            self.conn.send((req.rid, False, (type(e).__name__, str(e))))
+
+    # ------------------------------------------------------------------ the serve loop
+    def serve(self):
+        while True:
+            if self.inflight and not self.backlog and not self.conn.poll(0):  # nothing new to start: hand back the oldest launch
+                self.finish_oldest()
+                continue
+            msg = self.next_message()
+            if msg is None:
+                break
+            t_in = time.time()
+            req = self.take(msg)
+            if req.method in self.CONTROL:
+                self.control(req)
+                continue
+            requests, batchable = self.take_batch(req)
+            if batchable and self.pipelined:
+                self.place(requests, t_in)
+            else:
+                self.run_alone(requests, t_in)
+        self.drain()
+
+    def take_batch(self, first: _Request):
+        """-> (the requests of one launch, may it be a batch launch): `first` and, when the pipeline can batch it, the `infer` calls queued
+        behind it with the same options, up to `max_batch`.  While a launch is on the GPU a new one could not start anyway: a partial batch
+        then waits for more frames until that launch is (by the running average) about to finish -- the batch fills at no cost in latency.
+        With nothing in flight a frame is never held back."""
+        pipe, requests = self.pipe, [first]
+        batchable = self.max_batch > 1 and first.method == "infer" and len(first.args) == 1 and hasattr(pipe, "infer_batch")
         if batchable and hasattr(pipe, "can_batch"):
             try:
-                batchable = bool(pipe.can_batch(**kwargs))
+                batchable = bool(pipe.can_batch(**first.kwargs))
             except Exception:
                 batchable = False
-        if batchable:
-            # While a launch is on the GPU a new one could not start anyway: a partial batch then waits for more frames
-            # until that launch is (by the running average) about to finish -- the batch fills at no cost in latency.
-            # With nothing in flight a frame is never held back.
-            fill_until = (inflight[0][2] + 0.8 * ema_launch_s[0]) if (pipelined and inflight) else 0.0
-            while len(group_) < max_batch:
-                if not (backlog or conn.poll(0)):
-                    wait = fill_until - time.time()
-                    if wait <= 0 or not conn.poll(min(wait, 0.25)):
-                        break
-                try:
-                    nxt = backlog.pop(0) if backlog else conn.recv()
-                except (EOFError, OSError):
-                    nxt = None
-                if nxt is not None and nxt[1] == "infer" and len(nxt[2]) == 1 and same_options(nxt[3], kwargs):
-                    r2, _m, a2, _k, s2 = take(nxt)
-                    group_.append((r2, a2, s2))
-                    seeds_.append(_k.get("seed", 42))
-                    prompts_.append(_k.get("prompt", ["pixar, cg"]))
-                    opts_.append((_k.get("strength", 0.4), _k.get("controlnet_scale", 1)))
-                else:  # different options / another method / shutdown: serve it next, stop growing this batch
-                    backlog.insert(0, nxt)
+        if not batchable:
+            return requests, False
+        fill_until = (self.inflight[0].t_in + 0.8 * self.stats.ema_launch_s) if (self.pipelined and self.inflight) else 0.0
+        while len(requests) < self.max_batch:
+            if not (self.backlog or self.conn.poll(0)):
+                wait = fill_until - time.time()
+                if wait <= 0 or not self.conn.poll(min(wait, 0.25)):
                     break
-        if batchable and pipelined:
-            # launches in flight run on engines of THEIR plan: anything that re-prepares (other options, another prompt)
-            # waits for them (ADVICE r1: `_engine_for` / `set_text_embeds` under a running graph)
-            if inflight and not same_options(inflight[-1][3], kwargs):
-                # another session's frame: other prompts / sizes / step counts run BESIDE what is in flight (own plan, own
-                # prompt constants per lane); only a pipeline that says so (or cannot say) makes it wait
-                if not hasattr(pipe, "needs_idle") or pipe.needs_idle(**kwargs):
-                    drain()
-            # the LOWEST free lane (not round-robin): a lone frame always lands on lane 0 and one beside it on lane 1 -- the lanes
-            # whose launches may use a side stream for the ControlNet encoder (VideoSDPipeline._overlap_now)
-            busy = {e[4] for e in inflight}
-            lane = next(l for l in range(lanes) if l not in busy)
-            try:
-                handle = pipe.submit_batch([a[0] for _, a, _s in group_], lane=lane, **launch_options(kwargs, seeds_, prompts_, opts_))
-            except BaseException as e:
-                drain()
-                fail(group_, e)
-                continue
-            inflight.append((group_, handle, t_in, kwargs, lane))
-            if len(inflight) >= lanes:  # every lane has a launch on the GPU: hand back the oldest before taking more
-                finish_oldest()
-            continue
-        drain()  # anything else runs alone, after what is in flight
+            nxt = self.next_message()
+            if nxt is not None and nxt[1] == "infer" and len(nxt[2]) == 1 and self.same_options(nxt[3], first.kwargs):
+                requests.append(self.take(nxt))
+            else:  # different options / another method / shutdown: serve it next, stop growing this batch
+                self.backlog.insert(0, nxt)
+                break
+        return requests, True
+
+    def place(self, requests: List[_Request], t_in: float):
+        """One launch onto a lane.  Launches in flight run on engines of THEIR plan: anything that re-prepares (other options, another prompt)
+        waits for them (`_engine_for` / `set_text_embeds` under a running graph).  Another session's frame -- other prompts / sizes
+        / step counts -- runs BESIDE what is in flight (own plan, own prompt constants per lane); only a pipeline that says so (or cannot
+        say) makes it wait.  The lane is the LOWEST free one (not round-robin): a lone frame always lands on lane 0 and one beside it on
+        lane 1 -- the lanes whose launches may use a side stream for the ControlNet encoder (VideoSDPipeline._overlap_now).  When every lane
+        then has a launch on the GPU, the oldest is handed back before more is taken."""
+        pipe, kwargs = self.pipe, requests[0].kwargs
+        if self.inflight and not self.same_options(self.inflight[-1].kwargs, kwargs):
+            if not hasattr(pipe, "needs_idle") or pipe.needs_idle(**kwargs):
+                self.drain()
+        busy = {l.lane for l in self.inflight}
+        lane = next(l for l in range(self.lanes) if l not in busy)
         try:
-            if len(group_) > 1:
-                outs = pipe.infer_batch([a[0] for _, a, _s in group_], **launch_options(kwargs, seeds_, prompts_, opts_))
-                for (r, _a, s), o in zip(group_, outs):
-                    reply(r, o, s)
-                stats.add(len(group_), (time.time() - t_in) * 1e3)
-            else:
-                out = getattr(pipe, method)(*args, **kwargs)
-                reply(rid, out, slot)
-                if method == "infer":
-                    stats.add(1, (time.time() - t_in) * 1e3)
+            handle = pipe.submit_batch([r.args[0] for r in requests], lane=lane, **self.launch_options(requests))
         except BaseException as e:
-            fail(group_, e)
-    drain()
-    if dist is not None:
+            self.drain()
+            self.fail(requests, e)
+            return
+        self.inflight.append(_Launch(requests, handle, t_in, kwargs, lane))
+        if len(self.inflight) >= self.lanes:
+            self.finish_oldest()
+
+    def run_alone(self, requests: List[_Request], t_in: float):
+        """anything else runs alone, after what is in flight: a batch without the two-phase launch, one `infer`, any other method"""
+        self.drain()
+        first = requests[0]
         try:
-            dist.destroy_process_group()
-        except Exception:
-            pass
+            if len(requests) > 1:
+                outs = self.pipe.infer_batch([r.args[0] for r in requests], **self.launch_options(requests))
+            else:
+                outs = [getattr(self.pipe, first.method)(*first.args, **first.kwargs)]
+            for r, o in zip(requests, outs):
+                self.reply(r, o)
+            if len(requests) > 1 or first.method == "infer":
+                self.stats.add(len(requests), (time.time() - t_in) * 1e3)
+        except BaseException as e:
+            self.fail(requests, e)
+
+    def finish_oldest(self):
+        """collect the oldest launch and answer its requests, in request order"""
+        launch = self.inflight.pop(0)
+        stats = self.stats
+        try:
+            outs = self.pipe.collect_batch(launch.handle)
+            dt = time.time() - launch.t_in
+            stats.ema_launch_s = dt if stats.ema_launch_s == 0.0 else 0.8 * stats.ema_launch_s + 0.2 * dt
+            for r, o in zip(launch.requests, outs):
+                self.reply(r, o)
+            stats.add(len(launch.requests), (time.time() - launch.t_in) * 1e3)
+        except BaseException as e:
+            self.fail(launch.requests, e)
+
+    def drain(self):
+        while self.inflight:
+            self.finish_oldest()
 
 
+def _worker_main(conn, factory: str, config: Dict[str, Any], max_batch: int = 1, group: Optional[Dict[str, Any]] = None,
+                 shm: Optional[Dict[str, Any]] = None, lanes: int = 2):
+    """The worker process: build the worker (group rendezvous, pipeline, rings), say so, serve until the pipe ends, leave the group."""
+    try:
+        worker = _Worker(conn, factory, config, max_batch, group, shm, lanes)
+    except BaseException as e:  # construction errors travel to the parent (the reference re-raises KeyError)
+        conn.send(("error", (type(e).__name__, str(e))))
+        return
+    conn.send(("ready", None))
+    worker.serve()
+    worker.group.leave()
+
+
+# ----------------------------------------------------------------------------------------- the parent's side
 class _ReplyHub:
     """ONE thread reads the reply pipes of every RemotePipeline of the process (multiprocessing.connection.wait over all of
     them) and hands a whole batch of finished calls to their event loop in ONE wake-up.  Rounds 2-4 gave every worker a reader
@@ -671,10 +607,8 @@ class _ReplyHub:
         self._thread.start()
 
     def _wake(self):
-        try:
+        with suppress(OSError, ValueError):
             self._wake_w.send_bytes(b"x")
-        except (OSError, ValueError):
-            pass
 
     def add(self, p: "RemotePipeline"):
         with self._lock:
@@ -724,10 +658,8 @@ class _ReplyHub:
                     #  replies of every OTHER worker keep flowing through this one -- ADVICE r5)
                     threading.Thread(target=p._on_eof, name="vsd-reap", daemon=True).start()
             for loop, setters in batch.items():
-                try:
+                with suppress(RuntimeError):  # the caller's loop is gone
                     loop.call_soon_threadsafe(_run_setters, setters)  # one wake-up of the loop for the whole batch
-                except RuntimeError:  # the caller's loop is gone
-                    pass
 
 
 def _run_setters(setters):
@@ -866,13 +798,8 @@ class RemotePipeline:
         """batch (the reply hub): completions for an event loop are collected per loop and handed over in one wake-up"""
         target, loop, slot, _deadline = entry
         t0 = time.perf_counter()
-        if ok and isinstance(payload, tuple) and payload and payload[0] == "__shm__":
-            _, s, w, h = payload
-            payload = _image_from_slot(self._rings[1], s, w, h, copy=True)
-            self.host_s["frames"] += 1
-        elif ok and isinstance(payload, tuple) and payload and payload[0] == "__shm420__":
-            _, s, w, h = payload
-            payload = _i420_from_slot(self._rings[1], s, w, h, copy=True)
+        if ok and is_slot_ref(payload):
+            payload = decode_frame(self._rings[1], payload, copy=True)  # (the reply slot is free again when this returns)
             self.host_s["frames"] += 1
         t1 = time.perf_counter()
         self.host_s["slot_read"] += t1 - t0
@@ -887,10 +814,8 @@ class RemotePipeline:
         if loop is not None and batch is not None:
             batch.setdefault(loop, []).append(setter)
         elif loop is not None:
-            try:
+            with suppress(RuntimeError):  # the caller's loop is gone
                 loop.call_soon_threadsafe(setter)
-            except RuntimeError:  # the caller's loop is gone
-                pass
         else:
             setter()
         self.host_s["complete"] += time.perf_counter() - t1
@@ -907,10 +832,8 @@ class RemotePipeline:
     def _on_eof(self):
         """the reply pipe ended: the worker is gone (called by the reply hub's thread)"""
         with self._proc_lock:  # (one thread at a time reaps: a concurrent waitpid leaves `exitcode` unset)
-            try:
+            with suppress(Exception):
                 self._proc.join(timeout=5)  # `exitcode` / `is_alive` are settled when the callers wake up
-            except Exception:
-                pass
             code = self._proc.exitcode
         self._fail_all(WorkerDied(f"pipeline worker (pid {self._proc.pid}) died (exit code {code})"))
 
@@ -935,35 +858,27 @@ class RemotePipeline:
         if not self._ready:
             self.wait_ready()
         slot = None
-        if name == "infer" and len(args) == 1 and is_i420(args[0]):
+        frame = args[0] if name == "infer" and len(args) == 1 else None
+        if is_i420(frame) and not isinstance(frame, I420Frame):
             # a WebRTC frame crosses as I420: the three planes go straight into the request slot (two plane copies per frame in this
-            # process, out and back, and no arithmetic); too large for a slot or no slot free: pickled as an I420Frame.  The frame is
-            # checked BEFORE a slot is taken (another pixel format, a short plane: ValueError to the caller, no slot held).
-            f = args[0]
-            planes = (f.y, f.u, f.v) if isinstance(f, I420Frame) else av_plane_views(f)
-            h, w = planes[0].shape
-            if self._rings is not None and I420Frame.nbytes_for(w, h) <= self._rings[0].slot_bytes:
-                with self._lock:
-                    slot = self._free_slots.pop() if self._free_slots else None
-            if slot is not None:
-                t0 = time.perf_counter()
-                args = (("__shm420__",) + _i420_to_slot(self._rings[0], slot, planes, w, h),)
-                self.host_s["slot_write"] += time.perf_counter() - t0
-            else:
-                args = (f if isinstance(f, I420Frame) else I420Frame.from_planes(*planes),)
-        elif name == "infer" and self._rings is not None and len(args) == 1 and hasattr(args[0], "tobytes") and hasattr(args[0], "size"):
+            # process, out and back, and no arithmetic); too large for a slot, no slot free or no slot ring: pickled as an I420Frame.
+            # The frame is checked BEFORE a slot is taken (another pixel format, a short plane: ValueError to the caller, no slot held).
+            frame = av_plane_views(frame)
+        if self._rings is not None and (isinstance(frame, tuple) or is_frame(frame)):
             with self._lock:
                 slot = self._free_slots.pop() if self._free_slots else None
             if slot is not None:
                 t0 = time.perf_counter()
-                where = _image_to_slot(self._rings[0], slot, args[0])
+                ref = encode_frame(self._rings[0], slot, frame)
                 self.host_s["slot_write"] += time.perf_counter() - t0
-                if where is None:
+                if ref is None:  # it does not fit a slot: the slot goes back, the frame travels pickled
                     with self._lock:
                         self._free_slots.append(slot)
                     slot = None
                 else:
-                    args = (("__shm__",) + where,)
+                    args = (ref,)
+        if slot is None and isinstance(frame, tuple):
+            args = (I420Frame.from_planes(*frame),)
         deadline = None
         if self.call_timeout and name == "infer":
             deadline = time.time() + self.call_timeout
@@ -985,11 +900,9 @@ class RemotePipeline:
             # hand-over less (scripts/dispatch_ceiling.py).  Only while nothing is queued or being written by the writer thread:
             # a caller's messages reach the worker in the order it sent them.
             t0 = time.perf_counter()
-            try:
+            with suppress(OSError, ValueError, BrokenPipeError):  # the reader's EOF path reports the dead worker
                 with self._send_lock:
                     self._conn.send((rid, name, args, kwargs))
-            except (OSError, ValueError, BrokenPipeError):
-                pass  # the reader's EOF path reports the dead worker
             self.host_s["send"] += time.perf_counter() - t0
             return
         self._outbox.put((rid, name, args, kwargs))
@@ -999,15 +912,11 @@ class RemotePipeline:
             loop = asyncio.get_running_loop()
             fut = loop.create_future()
         except RuntimeError:
-            import concurrent.futures
-
             loop, fut = None, concurrent.futures.Future()
         self._send(name, args, kwargs, fut, loop)
         return fut
 
     def _submit_sync(self, name, args, kwargs):
-        import concurrent.futures
-
         fut = concurrent.futures.Future()
         self._send(name, args, kwargs, fut, None)
         return fut.result()
@@ -1028,15 +937,13 @@ class RemotePipeline:
 
     def _kill(self):
         with self._proc_lock:
-            try:
+            with suppress(Exception):
                 if self._proc.is_alive():
                     self._proc.kill()  # exactly this PID
                     self._proc.join(timeout=5)
-            except Exception:
-                pass
 
     def close(self):
-        try:
+        with suppress(Exception):
             if hasattr(self, "_outbox") and not self.dead:
                 with self._q_lock:
                     self._queued += 1
@@ -1044,17 +951,13 @@ class RemotePipeline:
                 self._writer.join(timeout=2)
             elif not self.dead:
                 self._conn.send(None)
-        except Exception:
-            pass
-        try:
+        with suppress(Exception):
             with self._proc_lock:  # (the reply hub's reaper may be joining the same process: one waitpid at a time)
                 if self._proc.is_alive():
                     self._proc.join(timeout=5)
                 if self._proc.is_alive():
                     self._proc.terminate()
                     self._proc.join(timeout=5)
-        except Exception:
-            pass
         self.dead = True
         self.death = self.death or WorkerDied("pipeline worker was closed")
         hub = _ReplyHub._inst  # (never MAKE a hub here: `close` also runs from __del__ while the interpreter shuts down)
@@ -1108,22 +1011,23 @@ def spawn_workers(n: int, factory: str = "videosd_amd.pipeline:VideoSDPipeline",
     return ws
 
 
+def _warm_kwargs(w, warm_options: Dict[str, Any]) -> Dict[str, Any]:
+    """`warm_up`'s arguments for handle `w`: every (batch size, lane) engine the stream will use"""
+    b = int(getattr(w, "max_batch", 1) or 1)
+    return dict(batches=tuple(range(1, b + 1)), lanes=getattr(w, "lanes", 2) if b > 1 else 1, **warm_options)
+
+
 def warm_group(ws: List["RemotePipeline"], warm_options: Dict[str, Any]):
     """Rank 0 warms up (plans, graphs, per-shape tuning) -> its kernel choices to every rank -> the others warm up."""
-    b = int(getattr(ws[0], "max_batch", 1) or 1)
-    kw = dict(batches=tuple(range(1, b + 1)), lanes=getattr(ws[0], "lanes", 2) if b > 1 else 1, **warm_options)
+    kw = _warm_kwargs(ws[0], warm_options)
     if len(ws) > 1 and all(getattr(w, "group", None) for w in ws):
         # rank 0 alone may time kernel candidates, and only now: afterwards every rank (rank 0 too) takes the deterministic
         # choice for a shape nobody has measured, so that frames of sizes that turn up later still get the same kernels everywhere
-        try:
+        with suppress(RemoteCallError):
             ws[0].method("set_tuning_mode")("auto")
-        except RemoteCallError:
-            pass
         ws[0].method("warm_up")(**kw)
-        try:
+        with suppress(RemoteCallError):
             ws[0].method("set_tuning_mode")("table")
-        except RemoteCallError:
-            pass
         for f in [w.sync_tuning.remote() for w in ws]:
             f.result(timeout=600)
         futs = [w.method("warm_up").remote(**kw) for w in ws[1:]]
@@ -1202,7 +1106,7 @@ class FrameDispatcher:
         return self.healthy[g] and not getattr(p, "dead", False) and (proc is None or proc.is_alive())
 
     def _sync_prompt(self, options):
-        prompt = options.get("prompt", ["pixar, cg"])  # the reference's default (videopipeline.py:78)
+        prompt = options.get("prompt", INFER_DEFAULTS["prompt"])
         key = prompt_key(prompt)
         if not self.group_ok and not self._had_group:
             return  # stand-alone handles: each worker encodes a prompt when its first frame with it arrives
@@ -1217,7 +1121,7 @@ class FrameDispatcher:
         # first frame with that prompt).  The race that remains -- a member dying inside the collective -- ends at the
         # workers' own short deadline (`sync_timeout`), after which they encode locally and report it.
         if self.group_ok and not all(self._member_alive(g) for g in range(self.n)):
-            self._group_broken(-1)
+            self._group_broken()
         if not self.group_ok:
             # No collective any more: ask every live worker ONCE per new prompt to encode it itself, ahead of its frames, and
             # remember the key like a synced one.  (Round 3 never recorded it, so after a single worker death EVERY frame posted a
@@ -1225,16 +1129,12 @@ class FrameDispatcher:
             # queued ahead of the frames: ADVICE r3.  A worker that misses the request -- respawned later -- encodes on demand at
             # its first frame with the prompt: VideoSDPipeline.submit_batch -> _cache_prompt.)
             with self._plock:
-                self._prompts_known[key] = True
-                while len(self._prompts_known) > self.max_prompts_known:
-                    self._prompts_known.popitem(last=False)
+                self._remember_prompt(key)
             self.local_prompt_requests += 1
             for g, p in enumerate(self.pipelines):
                 if self._member_alive(g) and hasattr(p, "sync_prompt"):
-                    try:
+                    with suppress(Exception):
                         p.sync_prompt.remote(prompt, None, collective=False)
-                    except Exception:
-                        pass
             return
         self.prompt_syncs += 1
         with self._plock:
@@ -1242,7 +1142,7 @@ class FrameDispatcher:
         header = {k: float(options[k]) for k in PROMPT_HEADER_KEYS if k in options and isinstance(options[k], (int, float))}
         state = {"left": self.n, "ok": True}
 
-        def done(f, g):
+        def done(f):
             # runs on a RemotePipeline's reader thread (one per worker), concurrently with the event-loop thread's lookups
             # above: every touch of the shared bookkeeping is under the lock (a lost decrement left the key pending
             # forever; concurrent OrderedDict mutation can corrupt the LRU order)
@@ -1254,28 +1154,32 @@ class FrameDispatcher:
                 if bad:
                     state["ok"] = False
                     self.prompt_sync_failures += 1
-                    self._group_broken(g)
+                    self._group_broken()
                 state["left"] -= 1
                 if state["left"] == 0:
                     self._prompts_pending.discard(key)
                     if state["ok"]:  # known only once EVERY member has it
-                        self._prompts_known[key] = True
-                        while len(self._prompts_known) > self.max_prompts_known:
-                            self._prompts_known.popitem(last=False)
+                        self._remember_prompt(key)
 
-        for g, p in enumerate(self.pipelines):
+        for p in self.pipelines:
             try:
                 fut = p.sync_prompt.remote(prompt, header)
-                fut.add_done_callback(lambda f, g=g: done(f, g))
+                fut.add_done_callback(done)
             except Exception:
                 with self._plock:
                     state["ok"] = False
                     state["left"] -= 1
                     if state["left"] == 0:
                         self._prompts_pending.discard(key)
-                    self._group_broken(g)
+                    self._group_broken()
 
-    def _group_broken(self, gpu):
+    def _remember_prompt(self, key):
+        """(under `_plock`) every worker holds `key` now; the least recently used one is forgotten beyond `max_prompts_known`"""
+        self._prompts_known[key] = True
+        while len(self._prompts_known) > self.max_prompts_known:
+            self._prompts_known.popitem(last=False)
+
+    def _group_broken(self):
         # a member is gone: the communicator cannot be repaired; every worker encodes for itself until the group is re-formed
         # (_maybe_regroup, after the member's replacement is up)
         self.group_ok = False
@@ -1321,7 +1225,7 @@ class FrameDispatcher:
             return
         self.healthy[gpu] = False
         if getattr(self.pipelines[gpu], "group", None):
-            self._group_broken(gpu)
+            self._group_broken()
         if self.respawn and hasattr(self.pipelines[gpu], "respawn") and not self._respawning[gpu]:
             self._respawning[gpu] = True
             asyncio.ensure_future(self._respawn(gpu))
@@ -1334,10 +1238,8 @@ class FrameDispatcher:
             if self.warm_options is not None:
                 from PIL import Image
 
-                b = int(getattr(new, "max_batch", 1) or 1)
-                try:  # every (batch size, lane) engine the stream will use
-                    await new.method("warm_up").remote(batches=tuple(range(1, b + 1)), lanes=getattr(new, "lanes", 2) if b > 1 else 1,
-                                                       **self.warm_options)
+                try:
+                    await new.method("warm_up").remote(**_warm_kwargs(new, self.warm_options))
                 except RemoteCallError:  # a pipeline without `warm_up`: one frame through `infer`
                     w, h = self.warm_options.get("width", 640), self.warm_options.get("height", 360)
                     await new.infer.remote(Image.new("RGB", (w, h)), **self.warm_options)
@@ -1374,10 +1276,8 @@ class FrameDispatcher:
                 self._prompts_pending.clear()
             self.group_ok = True
             self.regroups += 1
-            try:  # same kernels on every rank again (the replacement timed nothing of its own: it takes rank 0's choices)
+            with suppress(Exception):  # same kernels on every rank again (the replacement timed nothing of its own: it takes rank 0's choices)
                 await asyncio.wait_for(asyncio.gather(*[p.sync_tuning.remote() for p in self.pipelines]), timeout=120.0)
-            except Exception:
-                pass
         except Exception:
             self.regroup_failures += 1       # stand-alone workers, as before the attempt
         finally:
