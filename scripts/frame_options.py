@@ -76,10 +76,10 @@ def device_costs():
     """(c) and the zero-convs' kernel forms, on an engine of the real networks in this process"""
     from videosd_amd import lib as L
     from videosd_amd.ops import choose_tile
-    from videosd_amd.pipeline import _FRAME_OPTIONS
+    from videosd_amd.pipeline import PlanKey
 
     p = VideoSDPipeline(frame_options=True, tuning_mode="table", lanes=LANES, **MODEL)
-    eng = p._engine_for((512, 512, 4, 4, True, False, _FRAME_OPTIONS), PAIRS[0], BATCH, 0, prompt=p._cache_prompt("pixar, cg", prompt="pixar, cg"))
+    eng = p._engine_for(PlanKey(512, 512, 4, 4, True, False, frame_options=True), PAIRS[0], BATCH, 0, prompt=p._cache_prompt("pixar, cg", prompt="pixar, cg"))
     ops = eng.ops
     # which form the zero-convs (plain epilogue class: out_scale = 1, no residual) run in: their own table entry, or the heuristic
     tile_name = {v: k for k, v in vars(L).items() if k.startswith("TILE_") and isinstance(v, int)}

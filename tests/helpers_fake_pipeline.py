@@ -8,6 +8,17 @@ import torch
 from PIL import Image
 
 
+def bare_pipeline(**attrs):
+    """A real VideoSDPipeline without a GPU behind it -- every attribute declared (`_init_state`), no model loaded -- with `attrs` set
+    over them: enough for the decisions and checks that come before any device work."""
+    from videosd_amd.pipeline import VideoSDPipeline
+
+    p = VideoSDPipeline.__new__(VideoSDPipeline)
+    p._init_state({})
+    p.__dict__.update(attrs)
+    return p
+
+
 class FakePipeline:
     """Same `infer` surface as VideoSDPipeline; 'diffusion' = invert the image after an optional delay."""
 

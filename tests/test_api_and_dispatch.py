@@ -338,9 +338,8 @@ def test_two_rank_gloo_broadcast_and_sharding():
 def test_plan_cache_respects_its_memory_budget():
     """VideoSDPipeline._trim_memory: over the budget, idle programs go least recently used first, then the idle slots of the
     program being extended; the program's root and anything with a launch in flight stay."""
-    from collections import OrderedDict
-
-    from videosd_amd.pipeline import VideoSDPipeline
+    from helpers_fake_pipeline import bare_pipeline
+    from videosd_amd.pipeline import Launch, _Plan
 
     class E:
         def __init__(self, gb):
@@ -349,23 +348,24 @@ def test_plan_cache_respects_its_memory_budget():
         def _destroy_graphs(self):
             self.destroyed = True
 
-    p = VideoSDPipeline.__new__(VideoSDPipeline)
-    p._plans, p._outstanding, p.evictions = OrderedDict(), [], 0
+    p = bare_pipeline()
 
     def plan(*gbs):
         es = [E(g) for g in gbs]
-        return {"root": es[0], "opts": (0.6, 1.0), "engines": {(i + 1, 0): e for i, e in enumerate(es)}}
+        pl = _Plan(es[0], (0.6, 1.0))
+        pl.engines.update({(i + 1, 0): e for i, e in enumerate(es)})
+        return pl
 
     p._plans["old"], p._plans["busy"], p._plans["mid"], p._plans["cur"] = plan(6, 6), plan(5), plan(4), plan(3, 2, 2)
-    p._outstanding = [p._plans["busy"]["root"], p._plans["cur"]["engines"][(2, 0)]]
-    p._memory_used_and_limit = lambda before=None: (sum(e.gb for pl in p._plans.values() for e in pl["engines"].values()), 20)
+    p._in_flight = [Launch(e, 1, 0, None, False, ()) for e in (p._plans["busy"].root, p._plans["cur"].engines[(2, 0)])]
+    p._memory_used_and_limit = lambda before=None: (sum(e.gb for pl in p._plans.values() for e in pl.engines.values()), 20)
     assert p._trim_memory(keep="cur") == 2 and list(p._plans) == ["busy", "mid", "cur"]   # 28 -> 16: "old" alone is enough
-    p._memory_used_and_limit = lambda before=None: (sum(e.gb for pl in p._plans.values() for e in pl["engines"].values()), 9)
+    p._memory_used_and_limit = lambda before=None: (sum(e.gb for pl in p._plans.values() for e in pl.engines.values()), 9)
     cur = p._plans["cur"]
-    idle_slot = cur["engines"][(3, 0)]
+    idle_slot = cur.engines[(3, 0)]
     assert p._trim_memory(keep="cur") == 2                                                # "mid", then cur's one idle slot
-    assert list(p._plans) == ["busy", "cur"] and sorted(cur["engines"]) == [(1, 0), (2, 0)] and idle_slot.destroyed
-    assert not cur["root"].destroyed and not p._plans["busy"]["root"].destroyed and p.evictions == 4
+    assert list(p._plans) == ["busy", "cur"] and sorted(cur.engines) == [(1, 0), (2, 0)] and idle_slot.destroyed
+    assert not cur.root.destroyed and not p._plans["busy"].root.destroyed and p.evictions == 4
     assert p._trim_memory(keep="cur") == 0                                                # nothing idle left: allocation goes ahead
 
 
@@ -373,17 +373,19 @@ def test_side_stream_policy_is_a_function_of_the_launches_in_flight():
     """VideoSDPipeline._overlap_now: a launch runs its ControlNet encoder on the lane's side stream only while it has a
     command-processor pipe for it -- at most two launches in flight, all on lanes 0 / 1 (lane l's side stream is lane l + 2's
     own stream: videosd_amd/ops.py).  bench.py's engine legs state the same rule (`overlap_launch = slots < 3`)."""
-    from videosd_amd.pipeline import VideoSDPipeline
+    from helpers_fake_pipeline import bare_pipeline
+    from videosd_amd.pipeline import Launch
 
-    p = VideoSDPipeline.__new__(VideoSDPipeline)
+    p = bare_pipeline()
     os.environ.pop("VSD_OVERLAP_CN", None)
-    p._lanes_busy = []
+    busy = lambda *lanes: [Launch(None, 1, l, None, False, ()) for l in lanes]  # noqa: E731  (launches in flight on these lanes)
+    p._in_flight = busy()
     assert p._overlap_now(0) and p._overlap_now(1) and not p._overlap_now(2) and not p._overlap_now(3)
-    p._lanes_busy = [0]
+    p._in_flight = busy(0)
     assert p._overlap_now(1) and not p._overlap_now(2)
-    p._lanes_busy = [0, 1]
+    p._in_flight = busy(0, 1)
     assert not p._overlap_now(0) and not p._overlap_now(2)   # a third launch: three lanes busy
-    p._lanes_busy = [2]
+    p._in_flight = busy(2)
     assert not p._overlap_now(0)                             # lane 0's side stream IS lane 2's stream
 
 

@@ -417,7 +417,7 @@ def test_the_class_takes_options_per_frame(monkeypatch, tmp_path):
         assert _mad(o, s) < 0.5, _mad(o, s)
     assert _mad(outs[1], np.asarray(p.infer(imgs[1], strength=sa, controlnet_scale=ca, **base))) > 0.5  # the second frame really ran with ITS options
     assert all(e.plan["frame_options"] for e in p._engines.values()) and len(p._plans) == 1
-    assert all(pl["opts"] is None for pl in p._plans.values())
+    assert all(pl.opts is None for pl in p._plans.values())
     # a number keeps its meaning: every frame that value
     same = [np.asarray(o) for o in p.infer_batch(imgs, strength=sa, controlnet_scale=ca, **base)]
     assert np.array_equal(same[0], np.asarray(p.infer_batch(imgs, strength=[sa, sa], controlnet_scale=[ca, ca], **base)[0]))
@@ -463,7 +463,7 @@ def test_the_class_takes_options_per_frame(monkeypatch, tmp_path):
     del q
     # the unchanged default: the default program, one pair of options per launch, and the drain it needs
     r = FP._pipeline(monkeypatch)
-    assert not hasattr(r, "per_frame_options")
+    assert r.per_frame_options is False
     with pytest.raises(ValueError, match="frame_options=True"):
         r.infer_batch(imgs, strength=[sa, sb], controlnet_scale=ca, **base)
     r.infer_batch(imgs, strength=[sa, sa], controlnet_scale=ca, **base)  # (equal values are one pair)

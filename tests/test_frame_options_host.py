@@ -282,16 +282,9 @@ def test_worker_without_the_attribute_behaves_as_before():
 
 # ------------------------------------------------------------------------------------------ the class, before any device work
 def _bare_pipeline(**attrs):
-    from videosd_amd.pipeline import VideoSDPipeline
+    from helpers_fake_pipeline import bare_pipeline
 
-    p = VideoSDPipeline.__new__(VideoSDPipeline)
-    p.__dict__.update(dict(max_lanes=2, frame_prompts=False, frame_options=False, is_xl=False, honor_ref_flag=False, honor_controlnet_flag=False,
-                           device_resize=False, device_seed=False, _ref_img=None, _ref_epoch=0), **attrs)
-    from collections import OrderedDict, defaultdict
-
-    p._prompts, p._plans, p._outstanding, p._lanes_busy, p._host_ms = OrderedDict(), OrderedDict(), [], [], defaultdict(list)
-    p._cache_prompt = lambda key, **kw: None  # (no engine behind it)
-    return p
+    return bare_pipeline(_cache_prompt=lambda key, **kw: None, **attrs)  # (no engine behind it)
 
 
 def test_the_class_checks_options_before_any_device_work(tmp_path):

@@ -232,7 +232,7 @@ def test_the_class_takes_one_prompt_per_frame(monkeypatch, tmp_path):
     imgs = [Image.fromarray(_frame(H, W, seed=s), "RGB") for s in (3, 4)]
     a, b = "a watercolor painting", ["a charcoal sketch"]
     p = _pipeline(monkeypatch, frame_prompts=True)
-    assert p.per_frame_prompt is True and not hasattr(p, "per_frame_seed")
+    assert p.per_frame_prompt is True and p.per_frame_seed is False
     outs = [np.asarray(o) for o in p.infer_batch(imgs, prompts=[a, b], **opts)]
     singles = [np.asarray(p.infer(imgs[0], prompt=a, **opts)), np.asarray(p.infer(imgs[1], prompt=b, **opts))]
     for o, s in zip(outs, singles):
@@ -249,7 +249,7 @@ def test_the_class_takes_one_prompt_per_frame(monkeypatch, tmp_path):
     # more prompts than the cache holds, all of them in one launch: none is dropped while the launch needs it
     p.max_prompts = 1
     handle = p.submit_batch(imgs, prompts=["x", "y"], **opts)
-    assert {"x", "y"} <= set(p._prompts) and len(handle[4]) == 2
+    assert {"x", "y"} <= set(p._prompts) and len(handle.keep) == 2
     p.collect_batch(handle)
     del p
     # seeds and prompts per frame together
@@ -264,7 +264,7 @@ def test_the_class_takes_one_prompt_per_frame(monkeypatch, tmp_path):
     del q
     # the unchanged default
     r = _pipeline(monkeypatch)
-    assert not hasattr(r, "per_frame_prompt")
+    assert r.per_frame_prompt is False
     with pytest.raises(ValueError, match="frame_prompts=True"):
         r.infer_batch(imgs, prompts=[a, b], **opts)
     r.infer_batch(imgs, prompt=a, **opts)

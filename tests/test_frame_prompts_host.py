@@ -14,7 +14,7 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import frame_prompt_cases as FC  # noqa: E402
-from helpers_fake_pipeline import FakePipeline  # noqa: E402
+from helpers_fake_pipeline import FakePipeline, bare_pipeline as _bare_pipeline  # noqa: E402
 
 import videosd_amd.engine as E  # noqa: E402
 from videosd_amd import config as C  # noqa: E402
@@ -296,15 +296,6 @@ def test_worker_never_merges_a_frame_whose_strength_differs():
 
 
 # ------------------------------------------------------------------------------------------ error paths
-def _bare_pipeline(**attrs):
-    """a VideoSDPipeline without a GPU behind it: enough for the checks that come before any device work"""
-    from videosd_amd.pipeline import VideoSDPipeline
-
-    p = VideoSDPipeline.__new__(VideoSDPipeline)
-    p.__dict__.update(dict(max_lanes=2, frame_prompts=False, is_xl=False, honor_ref_flag=False, device_resize=False), **attrs)
-    return p
-
-
 def test_error_paths(world, tmp_path):
     imgs = [Image.new("RGB", (16, 16))] * 2
     with pytest.raises(ValueError, match="frame_prompts=True"):  # `prompts` without the switch

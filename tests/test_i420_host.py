@@ -211,8 +211,8 @@ def test_i420frame_to_rgb_and_from_rgb_are_the_contract():
 
 def test_the_class_sends_to_the_host_what_the_device_path_does_not_take():
     """VideoSDPipeline._i420_on_device (no GPU: the decision alone, as test_resample_host does for `_raw_frames`)"""
+    from helpers_fake_pipeline import bare_pipeline
     from videosd_amd.frames import I420Frame
-    from videosd_amd.pipeline import VideoSDPipeline
 
     class Ops:
         def i420_to_rgb(self): ...
@@ -222,8 +222,7 @@ def test_the_class_sends_to_the_host_what_the_device_path_does_not_take():
     class Model:
         ops = Ops()
 
-    p = VideoSDPipeline.__new__(VideoSDPipeline)
-    p.model, p.honor_ref_flag, p.is_xl = Model(), True, False
+    p = bare_pipeline(model=Model(), honor_ref_flag=True, is_xl=False)
     f = I420Frame.from_planes(*Y.yuv_frame((97, 131)))
     assert p._i420_on_device([f], 512, 512, False) is True
     assert p._i420_on_device([f], 150, 100, False) is False          # not a multiple of 8: the second Lanczos step stays on the host

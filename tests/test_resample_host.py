@@ -75,10 +75,9 @@ def test_which_frames_the_class_sends_down_the_device_path():
     (other modes, other target sizes, sides the kernel refuses, ops objects without the kernel such as tests/fake_ops.py)."""
     from types import SimpleNamespace
 
-    from videosd_amd.pipeline import VideoSDPipeline
+    from helpers_fake_pipeline import bare_pipeline
 
-    pipe = VideoSDPipeline.__new__(VideoSDPipeline)
-    pipe.model = SimpleNamespace(ops=SimpleNamespace(resample_rgb=lambda *a: None))
+    pipe = bare_pipeline(model=SimpleNamespace(ops=SimpleNamespace(resample_rgb=lambda *a: None)))
     rgb = Image.fromarray(R.frame((72, 128)), "RGB")
     raw = pipe._raw_frames([rgb, rgb], 64, 64)
     assert len(raw) == 2 and raw[0].shape == (72, 128, 3) and raw[0].dtype == np.uint8 and np.array_equal(raw[0], R.frame((72, 128)))

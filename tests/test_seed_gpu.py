@@ -307,7 +307,7 @@ def test_the_class_honours_seed_only_when_asked(monkeypatch):
     assert len(p._plans) == 1 and all(e.plan["device_seed"] for e in p._engines.values())
     del p
     q = _pipeline(monkeypatch)  # the unchanged default: `seed` is inert
-    assert not hasattr(q, "per_frame_seed")
+    assert q.per_frame_seed is False
     a = np.asarray(q.infer(img, seed=1, **opts))
     assert np.array_equal(np.asarray(q.infer(img, seed=2, **opts)), a)
     assert not any(e.plan["device_seed"] for e in q._engines.values())

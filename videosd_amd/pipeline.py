@@ -9,10 +9,14 @@ provided by videosd_amd/dispatch.py without Ray).
 What differs underneath: no diffusers / TensorRT / torch.compile; the frame goes through
 videosd_amd.engine.Engine (libvsd.so HIP kernels replayed as one hipGraph).
 """
+import gc
+import inspect
 import os
+import statistics
 import time
 import zlib
-from typing import Dict, List, Optional, Union
+from collections import OrderedDict
+from typing import Any, List, NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -22,6 +26,8 @@ from . import config as C
 from . import checkpoints as CK
 from . import weights as W
 from .frames import I420Frame, is_i420
+from .lcm import lcm_timesteps
+from .lib import RESAMPLE_MAX_SIDE
 
 
 def center_crop_resize(img: Image.Image, width: int, height: int) -> Image.Image:
@@ -40,95 +46,139 @@ def _weights_dir() -> Optional[str]:
     return d if d and os.path.isdir(d) else None
 
 
+def _flat(name: str) -> Optional[str]:
+    """`$VSD_WEIGHTS/<name>` (the flat layout), if it is there"""
+    d = _weights_dir()
+    return os.path.join(d, name) if d and os.path.exists(os.path.join(d, name)) else None
+
+
+def _text_files(mdir: Optional[str], tower: str, tokenizer: str, flat_tokenizer: Optional[str] = None):
+    """-> (checkpoint of a text tower or None, the directory of its vocabulary files): `<snapshot>/<tower>/model.safetensors` and
+    `<snapshot>/<tokenizer>/`, else flat under `$VSD_WEIGHTS`: `<tower>.safetensors`, the vocabulary in `flat_tokenizer/` or beside it."""
+    sub = os.path.join(mdir, tokenizer) if mdir else None
+    return (CK.checkpoint_file(mdir, tower, stems=("model",)) or _flat(tower + ".safetensors"),
+            sub if sub and os.path.isdir(sub) else (flat_tokenizer and _flat(flat_tokenizer)) or _weights_dir())
+
+
 def load_or_synthesize(spec, prefix: str, filename: str, device, snapshot_file: Optional[str] = None):
     """-> (weights, source).  In this order: the safetensors file of a `from_pretrained` directory (`snapshot_file`, found by
     weights.checkpoint_file), `$VSD_WEIGHTS/<filename>` (flat layout), seeded synthetic tensors (no checkpoint exists offline).
     A file that lacks a tensor of the architecture, or holds it in another shape, is refused with the tensor's name."""
-    d = _weights_dir()
-    path = snapshot_file or (os.path.join(d, filename) if d and os.path.exists(os.path.join(d, filename)) else None)
+    path = snapshot_file or _flat(filename)
     if path is not None:
         w = CK.load_safetensors(path, device=device)
         CK.check_against_spec(w, spec, path if snapshot_file else filename)
         return w, path
     return W.synthesize(spec, prefix, device=device), "synthetic"
 
-_FRAME_OPTIONS = ("frame_options", True)  # ... and in THAT mode (the last element when on)
-_FRAME_PROMPTS = ("frame_prompts", True)  # ... and in THAT mode (after _DEVICE_SEED when both are on)
-_DEVICE_SEED = ("device_seed", True)  # the element a plan key ends with in that mode (no prompt key of an SDXL plan looks like it)
+
+def _prompt_key(prompt):
+    """what the prompt cache (and an SDXL plan) knows a prompt by: the string, or the list as a tuple"""
+    return prompt if isinstance(prompt, str) else tuple(prompt)
+
+
+class PlanKey(NamedTuple):
+    """What a captured program depends on, and so what the plan cache is keyed by (`VideoSDPipeline._plan_key` builds it).  `strength` and
+    `controlnet_scale` are not in it: they only change constants the graph reads from device memory (Engine.update_options), so a slider
+    drag in the client (server.py:163-197) does not rebuild or re-capture anything -- only the NUMBER of timesteps they give is."""
+    height: int
+    width: int
+    steps: int
+    n_eff: int                   # timesteps of (strength, steps): the program's length
+    use_cn: bool
+    use_ref: bool
+    prompt: Any = None           # SDXL: the pooled text embedding is baked into the time embeddings at `prepare`, so the prompt is part of the program
+    device_seed: bool = False    # the three modes of Engine.prepare
+    frame_prompts: bool = False
+    frame_options: bool = False  # (the EFFECTIVE switch: SDXL and reference-only programs keep one pair of options per plan)
+
+
+class Launch(NamedTuple):
+    """The handle `submit_batch` returns and `collect_batch` takes; the pipeline keeps those not yet collected, oldest first."""
+    engine: Any
+    frames: int
+    lane: int
+    yuv: Optional[List[bool]]  # which results go back as I420 (None: none of them) ...
+    on_device: bool            # ... and whether the device converts them
+    keep: tuple                # the prompt blocks and option entries of the launch: their installs may not have executed yet
+
+
+class _Plan:
+    """One cached program: `root` owns the schedule constants, `engines` maps (frames per launch, lane) to the root and its slots, `opts` is
+    the (strength, controlnet_scale) those constants hold (None with `frame_options`: every frame slot of every engine has its own)."""
+
+    def __init__(self, root, opts):
+        self.root, self.opts, self.engines = root, opts, {}
+
+    def busy(self, in_flight) -> bool:
+        return any(h.engine is e for e in self.engines.values() for h in in_flight)
+
+    def destroy(self) -> int:
+        """release the graphs of every engine -> how many there were"""
+        for e in self.engines.values():
+            e._destroy_graphs()
+        return len(self.engines)
 
 
 class VideoSDPipeline:
     """One instance = one GPU = one full weight replica (the reference's Ray actor with num_gpus=1)."""
 
     def __init__(self, *args, **kwargs):
-        self.device = kwargs.get("device", 0)
-        self._kwargs = dict(kwargs)
-        self.honor_controlnet_flag = bool(kwargs.get("honor_controlnet_flag", False))  # extension, off by default
-        # extension, off by default: `ref=True` runs the reference-only mode (lcm_reference_pipeline.py, dead code at the
-        # reference's v2 where `ref` / `style_fidelity` are accepted and ignored, videopipeline.py:84-85)
-        self.honor_ref_flag = bool(kwargs.get("honor_ref_flag", False))
-        self._ref_img = None
-        self._ref_epoch = 0
-        # extension, off by default (a server should turn it on, INTEGRATION.md): the centre crop + LANCZOS resize in front of every
-        # frame (videopipeline.py:92-107) runs on the GPU instead of in PIL on this host thread -- the same bytes (csrc/resample.hip).
-        # RGB frames whose target size is a multiple of 8 take it; everything else keeps the host path.
-        self.device_resize = bool(kwargs.get("device_resize", False))
-        # extension, off by default: `seed` changes the picture.  The noise of every frame is drawn on the device from ITS seed
-        # (include/vsd.h THE NOISE CONTRACT; Engine.prepare(device_seed=True)); `infer_batch` / `submit_batch` take one seed per
-        # frame, and a worker coalesces frames that differ only in `seed` (`per_frame_seed`, read by dispatch.py).  Off: the
-        # reference's CPU-contract draws, the same for every frame and seed.
-        self.device_seed = bool(kwargs.get("device_seed", False))
-        if self.device_seed:
-            self.per_frame_seed = True
-        # extension, off by default: every frame of a launch has a prompt of its own -- `infer_batch` / `submit_batch` take `prompts`, one per
-        # frame, and a worker coalesces frames of sessions that differ in `prompt` (`per_frame_prompt`, read by dispatch.py).  The program
-        # then reads K / V^T per frame and runs every cross-attention in the explicit form (Engine.prepare(frame_prompts=True)).  Off:
-        # one prompt per launch, the absorbed form at the wide levels.
-        self.frame_prompts = bool(kwargs.get("frame_prompts", False))
-        if self.frame_prompts:
-            self.per_frame_prompt = True
-        # extension, off by default: every frame of a launch has a `strength` and a `controlnet_scale` of its own -- `infer_batch` /
-        # `submit_batch` take either as a number or as a sequence of one per frame, and a worker coalesces frames of sessions whose
-        # sliders stand differently (`per_frame_options` / `option_class`, read by dispatch.py).  The program then reads the scheduler
-        # coefficients, time tables and ControlNet scales per frame (Engine.prepare(frame_options=True)); a changed option rewrites a frame
-        # slot ahead of the launch, so nothing is drained.  Off: one (strength, controlnet_scale) per plan (`Engine.update_options`).
-        # SDXL and reference-only programs keep the default form either way.
-        self.frame_options = bool(kwargs.get("frame_options", False))
-        # launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on
-        # launch stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch
-        self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
+        self._init_state(kwargs)
         try:
             self.load_model(kwargs["model"], kwargs["controlnet"])
         except KeyError:
             print("Model name and controlnet model must be specified")  # videopipeline.py:24-26
             raise
-        if self.frame_options and self.is_xl:
-            self.frame_options = False
-        if self.frame_options:
-            self.per_frame_options = True
-        # Per-session state without stalls (server.py:90-93: options live on each VideoSDTrack; :132-137: every session's
-        # frames go through the same actors).  Two LRU caches:
-        #   prompts: prompt key -> PromptBlock (cross-attention K / V^T + absorbed weights of every layer, ~40 MB, built on the
-        #            GPU in ~1 ms); an engine takes a cached prompt with one device-to-device copy on its own stream;
-        #   plans:   (size, steps, timestep count, ControlNet, ref) -> {engines by (frames per launch, lane), constants}: each
-        #            plan has its own schedule constants, so sessions with different sizes / steps alternate frame by frame
-        #            with their graphs intact.  `max_plans` counts PROGRAMS.  Every engine owns its activation arena (1-6 GB
-        #            at 512x512, one to five frames per launch): `memory_budget` (fraction of the device's memory, default
-        #            0.6) bounds what the cache may hold -- least recently used idle programs go first, then the idle slots
-        #            of the program being extended (`_trim_memory`); an engine that is needed again is prepared again.
-        from collections import OrderedDict
+        self.frame_options = self.frame_options and not self.is_xl  # (SDXL programs keep the default form)
 
-        self._prompts = OrderedDict()
+    def _init_state(self, kwargs):
+        """Every attribute the object ever has, from the constructor kwargs alone: touches neither the GPU nor the library.  The switches
+        are extensions of the reference's surface, all off by default:
+        honor_controlnet_flag / honor_ref_flag: `controlnet` / `ref` of `infer` are obeyed, not accepted and ignored (videopipeline.py:84-85);
+            `ref=True` then runs the reference-only mode (lcm_reference_pipeline.py, dead code at the reference's v2).
+        device_resize (a server should turn it on): the centre crop + LANCZOS resize in front of every frame
+            (videopipeline.py:92-107) runs on the GPU instead of in PIL on this host thread -- the same bytes (csrc/resample.hip).  RGB frames
+            whose target size is a multiple of 8 take it; everything else keeps the host path.
+        device_seed: `seed` changes the picture: the noise of every frame is drawn on the device from ITS seed (include/vsd.h THE NOISE
+            CONTRACT), one seed per frame.  Off: the reference's CPU-contract draws, the same for every frame and seed.
+        frame_prompts: every frame of a launch has a prompt of its own (`prompts`, one per frame); the program then reads K / V^T per frame
+            and runs every cross-attention in the explicit form.  Off: one prompt per launch, the absorbed form at the wide levels.
+        frame_options: every frame of a launch has a `strength` and a `controlnet_scale` of its own (a number, or a sequence of one per frame);
+            the program then reads the scheduler coefficients, time tables and ControlNet scales per frame, and a changed option rewrites a
+            frame slot ahead of the launch, so nothing is drained.  Off: one pair per plan (`Engine.update_options`).  SDXL and
+            reference-only programs keep the default form either way.
+        The last three are modes of `Engine.prepare`; a worker coalesces frames that differ in what they make per-frame (`per_frame_*`).
+        lanes: launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on launch
+            stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch.
+        tuning_mode: "auto": shapes missing from the table are timed on this GPU at `prepare`; "table": never -- they take the deterministic
+            heuristic (ops.choose_tile), so that every rank of a group builds the SAME kernels and a frame's bits do not depend on the rank
+            it lands on (dispatch.spawn_workers sets this for groups; `sync_tuning` spreads rank 0's measured choices).
+        Per-session state without stalls (server.py:90-93: options live on each VideoSDTrack; :132-137: every session's frames go through
+        the same actors) is two LRU caches.  `_prompts`: prompt key -> PromptBlock (cross-attention K / V^T + absorbed weights of every
+        layer, ~40 MB, built on the GPU in ~1 ms); an engine takes a cached prompt with one device-to-device copy on its own stream.
+        `_plans`: PlanKey -> _Plan, each with its own schedule constants, so sessions with different sizes / steps alternate frame by frame
+        with their graphs intact; `max_plans` counts PROGRAMS.  Every engine owns its activation arena (1-6 GB at 512x512, one to five
+        frames per launch): `memory_budget` (fraction of the device's memory) bounds what the cache may hold (`_trim_memory`)."""
+        self._kwargs = dict(kwargs)
+        self.device = kwargs.get("device", 0)
+        for switch in ("honor_controlnet_flag", "honor_ref_flag", "device_resize", "device_seed", "frame_prompts", "frame_options"):
+            setattr(self, switch, bool(kwargs.get(switch, False)))
+        self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
+        self.tuning_mode = str(kwargs.get("tuning_mode", "auto"))
         self.max_prompts = int(kwargs.get("max_prompts", 8))
-        self._plans = OrderedDict()
         self.max_plans = int(kwargs.get("max_plans", 3))
         self.memory_budget = float(kwargs.get("memory_budget", 0.6))
-        self.evictions = 0
-        self._outstanding = []  # engines with a submitted, not yet collected launch
-        self._lanes_busy = []   # ... and the lane each of them runs on
-        self._host_ms = {"crop_resize": [], "upload_enqueue": [], "wait_download": [], "to_pil": [], "to_i420": [], "gpu": [], "prepare": [], "update_options": [],
-                         "prompt": []}
+        self.is_xl, self.unet_cfg, self.model, self.text_encoder, self.weight_sources, self._xl_prompts = False, C.SD15_UNET, None, None, {}, {}  # (`load_model`)
+        self._ref_img, self._ref_epoch = None, 0
+        self._prompts, self._plans, self.evictions = OrderedDict(), OrderedDict(), 0
+        self._in_flight: List[Launch] = []  # submitted, not yet collected
+        self._host_ms = {k: [] for k in ("crop_resize", "upload_enqueue", "wait_download", "to_pil", "to_i420", "gpu", "prepare", "update_options", "prompt")}
         self._io_bytes = {"up": None, "down": None}  # per frame of the last launch submitted / collected
+
+    per_frame_seed = property(lambda self: self.device_seed, doc="may a worker coalesce frames that differ in `seed`? (read by dispatch.py)")
+    per_frame_prompt = property(lambda self: self.frame_prompts, doc="... in `prompt`?")
+    per_frame_options = property(lambda self: self.frame_options, doc="... in `strength` / `controlnet_scale`, within one `option_class`?")
 
     # ------------------------------------------------------------------ model loading
     def load_model(self, model_name, controlnet_model="lllyasviel/control_v11p_sd15_canny"):
@@ -141,14 +191,7 @@ class VideoSDPipeline:
         ops = HipOps(int(self.device))
         dev = ops.device
         # per-shape kernel configurations found on an MI355X (shapes not in the table are timed at `prepare`)
-        tuning = os.environ.get("VSD_TUNING") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                              "profiles", "tuning_mi355x.json")
-        ops.load_tuning(tuning)
-        # "auto": shapes missing from the table are timed on this GPU at `prepare`; "table": never -- missing shapes take the
-        # deterministic heuristic (ops.choose_tile), so that every rank of a group builds the SAME kernels and a frame's bits
-        # do not depend on the rank it lands on (dispatch.spawn_workers sets this for groups; `sync_tuning` spreads rank 0's
-        # measured choices)
-        self.tuning_mode = str(getattr(self, "_kwargs", {}).get("tuning_mode", "auto"))
+        ops.load_tuning(os.environ.get("VSD_TUNING") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "tuning_mi355x.json"))
         # Extension (BASELINE.json configs[3]; the reference only knows SD1.5): a model name containing "xl" selects the
         # SDXL-base UNet topology (LCM-SDXL weights as `unet_sdxl.safetensors`, TAESD-XL as `taesdxl.safetensors`),
         # without a ControlNet tower; prompts then need 2048-wide embeddings + a 1280-wide pooled vector.
@@ -161,56 +204,32 @@ class VideoSDPipeline:
         # torch_dtype=float16.  Then the flat $VSD_WEIGHTS/*.safetensors files, then seeded synthetic tensors.  Like the
         # reference, a hub id that is not SimianLuo/LCM_Dreamshaper_v7 still gets that UNet (it hard-codes the id, :57); the VAE is
         # `madebyollin/taesd` (:68) unless the extension kwarg `vae=` names another directory.
-        kw = getattr(self, "_kwargs", {})
         mdir = CK.find_snapshot(model_name) or (None if self.is_xl else CK.find_snapshot("SimianLuo/LCM_Dreamshaper_v7"))
-        vdir = CK.find_snapshot(kw.get("vae") or ("madebyollin/taesdxl" if self.is_xl else "madebyollin/taesd"))
-        self.weight_sources = {}
+        vdir = CK.find_snapshot(self._kwargs.get("vae") or ("madebyollin/taesdxl" if self.is_xl else "madebyollin/taesd"))
         if self.is_xl:
-            wu, self.weight_sources["unet"] = load_or_synthesize(W.unet_spec(C.SDXL_UNET), "sdxl.", "unet_sdxl.safetensors", dev,
-                                                                 CK.checkpoint_file(mdir, "unet"))
-            wv, self.weight_sources["vae"] = load_or_synthesize(W.taesd_spec(C.TAESD), "vae.", "taesdxl.safetensors", dev,
-                                                                CK.checkpoint_file(vdir))
+            wu, self.weight_sources["unet"] = load_or_synthesize(W.unet_spec(C.SDXL_UNET), "sdxl.", "unet_sdxl.safetensors", dev, CK.checkpoint_file(mdir, "unet"))
+            wv, self.weight_sources["vae"] = load_or_synthesize(W.taesd_spec(C.TAESD), "vae.", "taesdxl.safetensors", dev, CK.checkpoint_file(vdir))
             self.model = Engine(ops, C.SDXL_UNET, None, C.TAESD, wu, None, wv)
             # the two text towers of an SDXL snapshot (<model>/text_encoder, <model>/text_encoder_2, tokenizer, tokenizer_2;
             # flat: $VSD_WEIGHTS/text_encoder.safetensors + text_encoder_2.safetensors, vocabulary files in $VSD_WEIGHTS[/tokenizer_2])
-            self.text_encoder, self._xl_prompts = None, {}
-            d = _weights_dir()
-
-            def flat(name):
-                return os.path.join(d, name) if d and os.path.exists(os.path.join(d, name)) else None
-
-            def sub(name):
-                return os.path.join(mdir, name) if mdir and os.path.isdir(os.path.join(mdir, name)) else None
-
-            f1 = CK.checkpoint_file(mdir, "text_encoder", stems=("model",)) or flat("text_encoder.safetensors")
-            f2 = CK.checkpoint_file(mdir, "text_encoder_2", stems=("model",)) or flat("text_encoder_2.safetensors")
-            self.weight_sources["text_encoder"] = f1 or "stand-in embeddings seeded by the prompt text"
-            self.weight_sources["text_encoder_2"] = f2 or "stand-in embeddings seeded by the prompt text"
+            (f1, tok1), (f2, tok2) = _text_files(mdir, "text_encoder", "tokenizer"), _text_files(mdir, "text_encoder_2", "tokenizer_2", "tokenizer_2")
+            self.weight_sources.update({k: f or "stand-in embeddings seeded by the prompt text" for k, f in (("text_encoder", f1), ("text_encoder_2", f2))})
             if f1 is not None and f2 is not None:
                 from . import clip as K
 
                 towers = []
-                for f, cfg, tok in ((f1, K.SDXL_CLIP_L, sub("tokenizer") or d),
-                                    (f2, K.SDXL_CLIP_G, sub("tokenizer_2") or (flat("tokenizer_2") or d))):
+                for f, cfg, tok in ((f1, K.SDXL_CLIP_L, tok1), (f2, K.SDXL_CLIP_G, tok2)):
                     wt = CK.load_safetensors(f, device=dev)
                     CK.check_against_spec(wt, K.text_tower_spec(cfg), f)
                     towers.append(K.ClipTextEncoder(ops, cfg, wt, tokenizer_dir=tok))
                 self.text_encoder = K.SdxlTextEncoders(*towers)
             return self.model
         cdir = CK.find_snapshot(controlnet_model)
-        wu, self.weight_sources["unet"] = load_or_synthesize(W.unet_spec(C.SD15_UNET), "unet.", "unet.safetensors", dev,
-                                                             CK.checkpoint_file(mdir, "unet"))
-        wc, self.weight_sources["controlnet"] = load_or_synthesize(W.controlnet_spec(C.SD15_CONTROLNET), "cn.", "controlnet.safetensors", dev,
-                                                                   CK.checkpoint_file(cdir))
-        wv, self.weight_sources["vae"] = load_or_synthesize(W.taesd_spec(C.TAESD), "vae.", "taesd.safetensors", dev,
-                                                            CK.checkpoint_file(vdir))
+        wu, self.weight_sources["unet"] = load_or_synthesize(W.unet_spec(C.SD15_UNET), "unet.", "unet.safetensors", dev, CK.checkpoint_file(mdir, "unet"))
+        wc, self.weight_sources["controlnet"] = load_or_synthesize(W.controlnet_spec(C.SD15_CONTROLNET), "cn.", "controlnet.safetensors", dev, CK.checkpoint_file(cdir))
+        wv, self.weight_sources["vae"] = load_or_synthesize(W.taesd_spec(C.TAESD), "vae.", "taesd.safetensors", dev, CK.checkpoint_file(vdir))
         self.model = Engine(ops, C.SD15_UNET, C.SD15_CONTROLNET, C.TAESD, wu, wc, wv)
-        self.text_encoder = None
-        d = _weights_dir()
-        clip_file = CK.checkpoint_file(mdir, "text_encoder", stems=("model",))
-        tok_dir = os.path.join(mdir, "tokenizer") if mdir and os.path.isdir(os.path.join(mdir, "tokenizer")) else d
-        if clip_file is None and d and os.path.exists(os.path.join(d, "text_encoder.safetensors")):
-            clip_file = os.path.join(d, "text_encoder.safetensors")
+        clip_file, tok_dir = _text_files(mdir, "text_encoder", "tokenizer")
         self.weight_sources["text_encoder"] = clip_file or "stand-in embeddings seeded by the prompt text"
         if clip_file is not None:
             from .clip import ClipTextEncoder
@@ -281,11 +300,13 @@ class VideoSDPipeline:
         return self._cache_prompt(key, embeds)
 
     def _prompts_in_use(self):
-        """ids of the cache entries a submitted, not yet collected launch of a `frame_prompts` engine reads from (its installs may not have
-        executed yet) -- the LRU never drops those"""
-        return {id(b) for e in self._outstanding for b in (e._prompt_slots.src if e._prompt_slots is not None else ()) if b is not None}
+        """ids of the cache entries a launch in flight on a `frame_prompts` engine reads (its installs may not have executed yet)"""
+        return {id(b) for h in self._in_flight for b in (h.engine._prompt_slots.src if h.engine._prompt_slots is not None else ()) if b is not None}
 
     def _cache_prompt(self, key, embeds=None, prompt=None, keep=()):
+        """The block of prompt `key`, built from `embeds` or from the text `prompt` when the cache lacks it (or holds other embeddings).  Over
+        `max_prompts` the least recently used entries go -- never `key`, never one of the launch being put together (`keep`), never one a
+        launch in flight reads: the cache then grows.  An engine that still holds an evicted block keeps it alive until it switches."""
         blk = self._prompts.get(key)
         if blk is not None and embeds is not None and blk.text is not None:
             # the same embeddings for a key this worker already holds (a repeated sync, a dispatcher that lost track of what the
@@ -299,15 +320,12 @@ class VideoSDPipeline:
             blk = self.model.build_prompt(embeds if embeds is not None else self.encode_prompt(prompt))
             self._prompts[key] = blk
             self._note("prompt", t0)
-            if getattr(self, "frame_prompts", False):
-                # (a launch names several entries: never one of the launch being put together (`keep`), never one in use -- the cache then grows)
+            if len(self._prompts) > max(1, self.max_prompts):
                 busy = self._prompts_in_use()
                 for k in [k for k, b in self._prompts.items() if k != key and k not in keep and id(b) not in busy]:
                     if len(self._prompts) <= max(1, self.max_prompts):
                         break
                     del self._prompts[k]
-            while not getattr(self, "frame_prompts", False) and len(self._prompts) > max(1, self.max_prompts):  # least recently used first; an engine that still holds an
-                self._prompts.popitem(last=False)                 # evicted block keeps it alive until it switches
         self._prompts.move_to_end(key)
         return blk
 
@@ -321,9 +339,7 @@ class VideoSDPipeline:
     def option_class(self, options) -> int:
         """What two requests must share to run in ONE launch of a `frame_options` pipeline although their `strength` / `controlnet_scale`
         differ: the NUMBER of timesteps of (strength, steps) -- the program's length (`options`: the kwargs of an `infer` call)."""
-        from .lcm import lcm_timesteps
-
-        return len(lcm_timesteps(float(options.get("strength", 0.4)), int(options.get("steps", 20))))
+        return len(lcm_timesteps(float(options.get("strength", INFER_DEFAULTS["strength"])), int(options.get("steps", INFER_DEFAULTS["steps"]))))
 
     @staticmethod
     def _per_frame(value, n: int, name: str):
@@ -342,8 +358,8 @@ class VideoSDPipeline:
     def _require_idle(self, what: str):
         """Prompt constants (cross-attention K / V^T) and plans are shared by every lane: rewriting them under a launch
         that is still running would hand that launch's caller another plan's frame."""
-        if self._outstanding:
-            raise RuntimeError(f"cannot {what} while {len(self._outstanding)} launch(es) are in flight: collect them first")
+        if self._in_flight:
+            raise RuntimeError(f"cannot {what} while {len(self._in_flight)} launch(es) are in flight: collect them first")
 
     def _note(self, what: str, t0: float):
         v = self._host_ms[what]
@@ -354,8 +370,6 @@ class VideoSDPipeline:
     def metrics(self):
         """Per-stage host / device milliseconds of this worker (medians over the last frames): where a frame's time goes
         between `infer` entry and the PIL image (per-stage ms per GPU)."""
-        import statistics
-
         out = {k: (round(statistics.median(v), 3) if v else None) for k, v in self._host_ms.items()}
         out["plans_cached"] = len(self._engines)
         out["programs_cached"] = len(self._plans)
@@ -371,7 +385,7 @@ class VideoSDPipeline:
         self._require_idle("profile")
         if not self._plans:
             raise RuntimeError("no plan prepared yet: call infer first")
-        eng = next(reversed(self._plans.values()))["root"]  # the most recently used program
+        eng = next(reversed(self._plans.values())).root  # the most recently used program
         ops = eng.ops
         eng.program.run()
         ops.synchronize()
@@ -415,17 +429,16 @@ class VideoSDPipeline:
         strength / controlnet_scale (objects built with `frame_options=True`): a number, or a sequence of one per frame; all strengths of a
         launch must give the same number of timesteps."""
         extra = {} if prompts is None else {"prompts": prompts}
-        return self.collect_batch(self.submit_batch(imgs, prompt=prompt, height=height, width=width, strength=strength,
-                                                    steps=steps, guidance_scale=guidance_scale, ref=ref,
-                                                    style_fidelity=style_fidelity, controlnet=controlnet, seed=seed,
-                                                    controlnet_scale=controlnet_scale, **extra))
+        return self.collect_batch(self.submit_batch(imgs, prompt=prompt, height=height, width=width, strength=strength, steps=steps,
+                                                    guidance_scale=guidance_scale, ref=ref, style_fidelity=style_fidelity,
+                                                    controlnet=controlnet, seed=seed, controlnet_scale=controlnet_scale, **extra))
 
     def warm_up(self, batches=(1,), lanes: int = 1, **options):
         """Prepare every (batch size, lane) engine a stream with these `infer` options will use -- plan, captured graph
         and one replay on black frames -- so that no frame of the stream pays for a `prepare` (tens of ms each, a
         visible stall in a 30 ms/frame stream).  A server calls it once per worker at start-up or after a respawn
         (`FrameDispatcher(warm_options=...)`); returns how many engines are ready."""
-        w, h = options.get("width", 640), options.get("height", 360)
+        w, h = options.get("width", INFER_DEFAULTS["width"]), options.get("height", INFER_DEFAULTS["height"])
         black = Image.new("RGB", (w, h))
         ready = 0
         for b in batches:
@@ -439,29 +452,61 @@ class VideoSDPipeline:
                      guidance_scale=7.5, ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1, prompts=None):
         """First half of `infer_batch`: crop / resize, upload, enqueue -- returns a handle for `collect_batch` without
         waiting for the GPU.  `lane` picks one of the prepared engines of that (options, batch size): two lanes keep two
-        launches in flight while the host works on the frames around them (the worker loop of dispatch.py does that)."""
+        launches in flight while the host works on the frames around them (the worker loop of dispatch.py does that).  Six phases in this
+        order -- prompts, frames, switches and options, seeds, engine and installs, enqueue: what is refused is refused before any device work."""
         if not 0 <= int(lane) < self.max_lanes:
             raise ValueError(f"lane {lane}: this pipeline was built for {self.max_lanes} launch lane(s) (kwarg `lanes`)")
+        prompt, plist = self._launch_prompts(len(imgs), prompt, prompts, ref)
+        t0 = time.perf_counter()
+        imgs, raw, i420, yuv, height, width = self._launch_frames(imgs, width, height, ref)
+        self._note("crop_resize", t0)
+        if plist is not None:  # one cache entry per frame (the same object for equal prompts)
+            keys = [_prompt_key(p) for p in plist]
+            pblock = [self._cache_prompt(k, prompt=p, keep=keys) for k, p in zip(keys, plist)]
+        else:
+            pblock = self._cache_prompt(_prompt_key(prompt), prompt=prompt)  # cached: nothing to do; new: ~1 ms on the GPU, nobody waits
+        key, pairs = self._launch_options(imgs, raw, strength, controlnet_scale,
+                                          dict(prompt=prompt, height=height, width=width, steps=steps, ref=ref, controlnet=controlnet))
+        seeds = self._launch_seeds(seed, len(imgs))
+        eng = self._engine_for(key, pairs[0], len(imgs), lane, prompt=pblock, prompt_text=prompt)
+        self._install(eng, key, pblock, pairs)
+        np.random.seed(seed if seeds is None else seeds[0] & 0xFFFFFFFF)  # kept for parity with videopipeline.py:112 (nothing downstream consumes it)
+        t0 = time.perf_counter()
+        self._enqueue(eng, lane, imgs, raw, i420, width, height, seeds)
+        handle = Launch(eng, len(imgs), int(lane), yuv if any(yuv) else None, i420 is not None,
+                        (tuple(pblock) if plist is not None else ()) + (tuple(e for e, _c in eng._want_opts) if key.frame_options else ()))
+        self._in_flight.append(handle)
+        self._note("upload_enqueue", t0)
+        return handle
+
+    def _launch_prompts(self, n: int, prompt, prompts, ref):
+        """Phase 1 -> (the launch's `prompt`, one prompt per frame or None in the one-prompt-per-launch mode)."""
         plist = None
         if prompts is not None:
-            if not getattr(self, "frame_prompts", False):
+            if not self.frame_prompts:
                 raise ValueError("prompts= (one prompt per frame) needs a pipeline built with frame_prompts=True; this one runs one prompt per launch (`prompt`)")
             plist = list(prompts)
-            if len(plist) != len(imgs):
-                raise ValueError(f"prompts must hold one prompt per frame: {len(plist)} prompt(s) for {len(imgs)} frame(s)")
-        elif getattr(self, "frame_prompts", False):
-            plist = [prompt] * len(imgs)
-        if plist is not None:
-            pkeys = [p if isinstance(p, str) else tuple(p) for p in plist]
-            if len(set(pkeys)) > 1 and (self.is_xl or (bool(ref) and self.honor_ref_flag)):
-                raise ValueError("prompts: more than one distinct prompt in a launch is not possible here: " +
-                                 ("an SDXL program has the pooled text embedding of ITS prompt baked in" if self.is_xl else
-                                  "reference-only frames run one frame per launch"))
-            prompt = plist[0]
-        t0 = time.perf_counter()
-        # WebRTC frames (planar YUV 4:2:0: an `I420Frame`, or an av.VideoFrame by duck typing): when EVERY frame of the launch is one,
-        # the planes go to the device as they are and the result comes back as I420 (`_i420_on_device`); otherwise such a frame is
-        # converted here by the host loop of the same colour contract and takes the path of a PIL image -- the same bytes either way.
+            if len(plist) != n:
+                raise ValueError(f"prompts must hold one prompt per frame: {len(plist)} prompt(s) for {n} frame(s)")
+        elif self.frame_prompts:
+            plist = [prompt] * n
+        if plist is None:
+            return prompt, None
+        if len({_prompt_key(p) for p in plist}) > 1 and (self.is_xl or (bool(ref) and self.honor_ref_flag)):
+            raise ValueError("prompts: more than one distinct prompt in a launch is not possible here: " +
+                             ("an SDXL program has the pooled text embedding of ITS prompt baked in" if self.is_xl else
+                              "reference-only frames run one frame per launch"))
+        return plist[0], plist
+
+    def _launch_frames(self, imgs, width: int, height: int, ref):
+        """Phase 2 -> (frames, raw, i420, yuv, height, width): which of the three input paths the launch takes, and its size.
+        WebRTC frames (planar YUV 4:2:0: an `I420Frame`, or an av.VideoFrame by duck typing; `yuv` says which are): when EVERY frame of the
+        launch is one, the planes go to the device as they are and the result comes back as I420 (`i420`, see `_i420_on_device`); otherwise
+        such a frame is converted here by the host loop of the same colour contract and takes the path of a PIL image -- the same bytes either
+        way.  `raw`: `device_resize` takes the frames as they came (`_raw_frames`); neither: cropped / resized here.
+        A size that is not a multiple of the VAE stride: `VaeImageProcessor.preprocess` (lcm_controlnet.py:457, 230) rounds it DOWN to a
+        multiple of 8 with a Lanczos resize and the pipeline returns that size.  (There the control image is the Sobel map of the unrounded
+        frame, resized; here it is the Sobel map of the rounded frame -- sizes the client offers are multiples of 8.)"""
         yuv = [is_i420(im) for im in imgs]
         i420 = None
         if any(yuv):
@@ -473,104 +518,95 @@ class VideoSDPipeline:
         raw = self._raw_frames(imgs, width, height) if self.device_resize and i420 is None else None
         if raw is None and i420 is None:
             imgs = [center_crop_resize(im, width, height) for im in imgs]
-        # A size that is not a multiple of the VAE stride: `VaeImageProcessor.preprocess` (lcm_controlnet.py:457, 230) rounds it
-        # DOWN to a multiple of 8 with a Lanczos resize and the pipeline returns that size.  (There the control image is the
-        # Sobel map of the unrounded frame, resized; here it is the Sobel map of the rounded frame -- sizes the client offers
-        # are multiples of 8.)
         if height % 8 or width % 8:
             height, width = height - height % 8, width - width % 8
             if height <= 0 or width <= 0:
                 raise ValueError("height and width must be at least 8")
             imgs = [im.resize((width, height), resample=Image.Resampling.LANCZOS) for im in imgs]
-        self._note("crop_resize", t0)
-        pkey = prompt if isinstance(prompt, str) else tuple(prompt)
-        if plist is not None:  # one cache entry per frame (the same object for equal prompts)
-            pblock = [self._cache_prompt(k, prompt=p, keep=pkeys) for k, p in zip(pkeys, plist)]
-        else:
-            pblock = self._cache_prompt(pkey, prompt=prompt)  # cached: nothing to do; new: ~1 ms on the GPU, nobody waits
-        use_cn = False if self.is_xl else (bool(controlnet) if self.honor_controlnet_flag else True)
-        use_ref = bool(ref) and self.honor_ref_flag and not self.is_xl
-        if use_ref:
-            if len(imgs) != 1:
-                raise ValueError("ref=True: one frame per call (the reference-only program runs one frame per launch)")
-            use_cn = False  # the reference-only pipeline has no ControlNet (lcm_reference_pipeline.py:855-890)
-            if self._ref_img is None:
-                self._ref_img = imgs[0] if raw is None else center_crop_resize(imgs[0], width, height)  # (stored as the host path stores it)
-                self._ref_epoch += 1
-        # The captured program depends on the frame size, the NUMBER of timesteps and the ControlNet switch; `strength`
-        # and `controlnet_scale` only change constants the graph reads from device memory (Engine.update_options): a
-        # slider drag in the client (server.py:163-197) does not rebuild or re-capture anything.
-        from .lcm import lcm_timesteps
+        return imgs, raw, i420, yuv, height, width
 
-        # per-frame options: one (strength, controlnet_scale) per frame; the launch's program is fixed by their COMMON number of timesteps
-        strengths = self._per_frame(strength, len(imgs), "strength")
-        cn_scales = self._per_frame(controlnet_scale, len(imgs), "controlnet_scale")
-        frame_opts = bool(getattr(self, "frame_options", False)) and not self.is_xl and not use_ref
+    def _switches(self, controlnet, ref):
+        """-> (use_cn, use_ref, frame_options in effect) for a frame with these `infer` flags.  SDXL has no ControlNet tower and the
+        reference-only pipeline no ControlNet (lcm_reference_pipeline.py:855-890); both keep one pair of options per plan."""
+        use_ref = bool(ref) and self.honor_ref_flag and not self.is_xl
+        use_cn = not self.is_xl and not use_ref and (bool(controlnet) if self.honor_controlnet_flag else True)
+        return use_cn, use_ref, self.frame_options and not self.is_xl and not use_ref
+
+    def _plan_key(self, o) -> PlanKey:
+        """The program a frame with the `infer` options `o` (all of them present, `strength` a number) runs on this object: the ONE place
+        a key is built, for the launch (`submit_batch`) and for the question whether it must wait (`needs_idle`)."""
+        use_cn, use_ref, frame_opts = self._switches(o["controlnet"], o["ref"])
+        return PlanKey(o["height"] - o["height"] % 8, o["width"] - o["width"] % 8, int(o["steps"]),
+                       len(lcm_timesteps(float(o["strength"]), int(o["steps"]))), use_cn, use_ref,
+                       _prompt_key(o["prompt"]) if self.is_xl else None, self.device_seed, self.frame_prompts, frame_opts)
+
+    def _launch_options(self, imgs, raw, strength, controlnet_scale, o):
+        """Phase 3 -> (the PlanKey of the launch, one (strength, controlnet_scale) per frame); `o`: the other options the key depends on.
+        The launch's program is fixed by the COMMON number of timesteps of its strengths.  The first frame seen with an honoured
+        `ref=True` becomes the reference image, stored as the host path stores it."""
+        n = len(imgs)
+        _use_cn, use_ref, frame_opts = self._switches(o["controlnet"], o["ref"])
+        if use_ref:
+            if n != 1:
+                raise ValueError("ref=True: one frame per call (the reference-only program runs one frame per launch)")
+            if self._ref_img is None:
+                self._ref_img = imgs[0] if raw is None else center_crop_resize(imgs[0], o["width"], o["height"])
+                self._ref_epoch += 1
+        strengths = self._per_frame(strength, n, "strength")
+        cn_scales = self._per_frame(controlnet_scale, n, "controlnet_scale")
         if not frame_opts and (len(set(strengths)) > 1 or len(set(cn_scales)) > 1):
             raise ValueError("strength / controlnet_scale with different values per frame need a pipeline built with frame_options=True "
                              "(and neither an SDXL nor a reference-only program): this launch runs one pair of options")
-        counts = [len(lcm_timesteps(v, int(steps))) for v in dict.fromkeys(strengths)]  # ValueError for an empty schedule: the caller's problem
+        key = self._plan_key(dict(o, strength=strengths[0]))  # ValueError for an empty schedule: the caller's problem
+        counts = [key.n_eff] + [len(lcm_timesteps(v, key.steps)) for v in dict.fromkeys(strengths[1:])]
         if len(set(counts)) > 1:
-            raise ValueError(f"the strengths {strengths} give different numbers of timesteps at steps={int(steps)} ({sorted(set(counts))}): "
+            raise ValueError(f"the strengths {strengths} give different numbers of timesteps at steps={key.steps} ({sorted(set(counts))}): "
                              "the frames of one launch run one program; launch them separately")
-        strength, controlnet_scale = strengths[0], cn_scales[0]
-        n_eff = counts[0]
-        # (SDXL: the pooled text embedding is baked into the time embeddings at `prepare`, so the prompt is part of the program)
-        plan_key = (height, width, int(steps), n_eff, use_cn, use_ref) + ((pkey,) if self.is_xl else ()) + ((_DEVICE_SEED,) if getattr(self, "device_seed", False) else ()) + ((_FRAME_PROMPTS,) if plist is not None else ()) + ((_FRAME_OPTIONS,) if frame_opts else ())
-        seeds = None
-        if getattr(self, "device_seed", False):
-            seeds = [seed] * len(imgs) if isinstance(seed, (int, np.integer)) else list(seed)
-            if len(seeds) != len(imgs) or not all(isinstance(v, (int, np.integer)) for v in seeds):
-                raise ValueError(f"seed must be an int or a sequence of {len(imgs)} ints (one per frame)")
-            seeds = [int(v) for v in seeds]
-        opts = (float(strength), float(controlnet_scale))
-        eng = self._engine_for(plan_key, opts, len(imgs), lane, prompt=pblock, prompt_text=prompt)
-        # this lane's launch reads ITS copy of the constants: the other lanes may run other prompts
-        eng.use_prompts(pblock) if plist is not None else eng.use_prompt(pblock)
-        if frame_opts:  # (a changed frame slot is rewritten on this lane's stream ahead of the program: nobody waits)
-            eng.use_options(list(zip(strengths, cn_scales)))
-        if use_ref and eng._ref_epoch != self._ref_epoch:
-            rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), width, height), dtype=np.uint8)
+        return key, list(zip(strengths, cn_scales))
+
+    def _launch_seeds(self, seed, n: int):
+        """Phase 4 -> one int per frame with `device_seed`; None without (engines of the default mode, and stand-ins, are called as before)"""
+        if not self.device_seed:
+            return None
+        seeds = [seed] * n if isinstance(seed, (int, np.integer)) else list(seed)
+        if len(seeds) != n or not all(isinstance(v, (int, np.integer)) for v in seeds):
+            raise ValueError(f"seed must be an int or a sequence of {n} ints (one per frame)")
+        return [int(v) for v in seeds]
+
+    def _install(self, eng, key: PlanKey, pblock, pairs):
+        """Phase 5, after `_engine_for`: this lane's launch reads ITS copy of the constants (the other lanes may run other prompts); a changed
+        frame slot is rewritten on this lane's stream ahead of the program, so nobody waits."""
+        eng.use_prompts(pblock) if isinstance(pblock, list) else eng.use_prompt(pblock)
+        if key.frame_options:
+            eng.use_options(pairs)
+        if key.use_ref and eng._ref_epoch != self._ref_epoch:
+            rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), key.width, key.height), dtype=np.uint8)
             eng.ops.upload(eng.ref_u8, torch.from_numpy(np.array(rf, copy=True)))  # (PIL's buffer is read-only)
             eng._ref_epoch = self._ref_epoch
-        np.random.seed(seed if seeds is None else seeds[0] & 0xFFFFFFFF)  # kept for parity with videopipeline.py:112 (nothing downstream consumes it)
-        t0 = time.perf_counter()
-        skw = {} if seeds is None else {"seeds": seeds}  # (engines of the default mode, and stand-ins, are called as before)
+
+    def _enqueue(self, eng, lane, imgs, raw, i420, width, height, seeds):
+        """Phase 6: upload and launch by the path `_launch_frames` chose; counts the bytes handed to the host-to-device copy per frame"""
+        skw = dict(overlap=self._overlap_now(lane), **({} if seeds is None else {"seeds": seeds}))
         if i420 is not None:
-            eng.submit_raw_i420(i420[0] if len(i420) == 1 else i420, overlap=self._overlap_now(lane), **skw)
+            eng.submit_raw_i420(i420[0] if len(i420) == 1 else i420, **skw)
             up = eng.last_upload_bytes
         elif raw is not None:
-            eng.submit_raw_u8(raw[0] if len(raw) == 1 else raw, overlap=self._overlap_now(lane), **skw)
+            eng.submit_raw_u8(raw[0] if len(raw) == 1 else raw, **skw)
             up = sum((b[2] - b[0]) * (b[3] - b[1]) * 3 for b in (eng.ops.center_crop_box(f.shape[1], f.shape[0], width, height) for f in raw))
         else:
             frames = np.stack([np.asarray(im if im.mode == "RGB" else im.convert("RGB"), dtype=np.uint8) for im in imgs])
-            eng.submit_u8(frames[0] if len(imgs) == 1 else frames, overlap=self._overlap_now(lane), **skw)
+            eng.submit_u8(frames[0] if len(imgs) == 1 else frames, **skw)
             up = frames.nbytes
-        self._io_bytes["up"] = up // len(imgs)  # bytes handed to the host-to-device copy per frame of this launch (counted, not timed)
-        self._outstanding.append(eng)
-        self._lanes_busy.append(int(lane))
-        self._note("upload_enqueue", t0)
-        if frame_opts:  # (the handle keeps the launch's prompt and option entries alive: their installs may not have executed yet)
-            return (eng, len(imgs), yuv if any(yuv) else None, i420 is not None, tuple(pblock) if plist is not None else (),
-                    tuple(e for e, _c in eng._want_opts))
-        if plist is not None:  # (the handle keeps the launch's cache entries alive: their installs may not have executed yet)
-            return (eng, len(imgs), yuv if any(yuv) else None, i420 is not None, tuple(pblock))
-        if any(yuv):  # (which results go back as I420, and whether the device converts them)
-            return (eng, len(imgs), yuv, i420 is not None)
-        return (eng, len(imgs))
+        self._io_bytes["up"] = up // len(imgs)  # (counted, not timed)
 
     def _i420_on_device(self, frames, width: int, height: int, ref) -> bool:
         """Do these `I420Frame`s take the device path (`Engine.submit_raw_i420` / `collect_i420`)?  Not what `_raw_frames` sends to the
         host either: a target size that is not a multiple of 8, `ref=True` on an object that honours it, an ops object without the
         kernels, a side above the limit.  Independent of `device_resize`: a new input type has no earlier behaviour to keep."""
-        from .lib import RESAMPLE_MAX_SIDE
-
         ops = getattr(self.model, "ops", None)
         if height % 8 or width % 8 or height <= 0 or width <= 0 or not all(hasattr(ops, a) for a in ("i420_to_rgb", "rgb_to_i420", "resample_rgb")):
             return False
-        if bool(ref) and self.honor_ref_flag and not self.is_xl:
-            return False
-        if max(height, width) > RESAMPLE_MAX_SIDE:
+        if (bool(ref) and self.honor_ref_flag and not self.is_xl) or max(height, width) > RESAMPLE_MAX_SIDE:
             return False
         return all(max(f.size) <= RESAMPLE_MAX_SIDE for f in frames)
 
@@ -578,11 +614,7 @@ class VideoSDPipeline:
         """`device_resize`: the frames as uint8 [h][w][3] arrays for `Engine.submit_raw_u8`, or None when this call keeps the host
         path: a frame that is not RGB, a target size that is not a multiple of 8 (the second Lanczos step below), a side the
         kernel refuses, an ops object without the kernel."""
-        from .lib import RESAMPLE_MAX_SIDE
-
-        if height % 8 or width % 8 or height <= 0 or width <= 0 or not hasattr(getattr(self.model, "ops", None), "resample_rgb"):
-            return None
-        if max(height, width) > RESAMPLE_MAX_SIDE:
+        if height % 8 or width % 8 or height <= 0 or width <= 0 or not hasattr(getattr(self.model, "ops", None), "resample_rgb") or max(height, width) > RESAMPLE_MAX_SIDE:
             return None
         for im in imgs:
             if getattr(im, "mode", None) != "RGB" or min(im.size) < 1 or max(im.size) > RESAMPLE_MAX_SIDE:
@@ -596,98 +628,70 @@ class VideoSDPipeline:
         lanes busy the side streams ARE the other lanes' streams and the launch stays on its own."""
         if os.environ.get("VSD_OVERLAP_CN") is not None:
             return os.environ.get("VSD_OVERLAP_CN") == "1"
-        return int(lane) < 2 and all(l < 2 for l in self._lanes_busy) and len(self._lanes_busy) < 2
+        return int(lane) < 2 and all(h.lane < 2 for h in self._in_flight) and len(self._in_flight) < 2
 
-    def collect_batch(self, handle):
-        eng, n = handle[:2]
-        yuv, on_device = (handle[2], handle[3]) if len(handle) > 2 else (None, False)
+    def collect_batch(self, handle: Launch):
+        """Second half of `infer_batch`: wait for the launch of `handle`, bring its frames back -> PIL images, or I420Frames where I420 came in"""
+        eng, n, yuv, on_device = handle.engine, handle.frames, handle.yuv, handle.on_device
         t0 = time.perf_counter()
         try:
             out = eng.collect_i420() if on_device else eng.collect_u8()
         finally:
-            if eng in self._outstanding:
-                i = self._outstanding.index(eng)
-                self._outstanding.pop(i)
-                self._lanes_busy.pop(i)
+            self._in_flight[:] = [h for h in self._in_flight if h is not handle]
         self._note("wait_download", t0)
         self._io_bytes["down"] = (eng.last_download_bytes if on_device else out.nbytes) // n
         if eng.last_gpu_ms is not None:
             self._host_ms["gpu"].append(eng.last_gpu_ms)
-        if on_device:
-            t0 = time.perf_counter()
-            res = [out] if n == 1 else out
-            self._note("to_i420", t0)  # (the conversion ran on the device: nothing is left for the host)
-            return res
-        out = out[None] if n == 1 else out
         t0 = time.perf_counter()
-        if yuv is None:
-            res = [Image.fromarray(o, mode="RGB") for o in out]
-            self._note("to_pil", t0)
-            return res
-        res = [I420Frame.from_rgb(o) if k else Image.fromarray(o, mode="RGB") for o, k in zip(out, yuv)]
-        self._note("to_i420", t0)
+        if on_device:  # (the conversion ran on the device: nothing is left for the host)
+            res = [out] if n == 1 else out
+        else:
+            res = [I420Frame.from_rgb(o) if k else Image.fromarray(o, mode="RGB") for o, k in zip(out[None] if n == 1 else out, yuv or [False] * n)]
+        self._note("to_pil" if yuv is None else "to_i420", t0)
         return res
 
     @property
     def _engines(self):
         """(plan_key, frames per launch, lane) -> prepared engine, over all cached plans"""
-        return {(pk, b, l): e for pk, pl in self._plans.items() for (b, l), e in pl["engines"].items()}
-
-    def _plan_busy(self, plan) -> bool:
-        return any(e in self._outstanding for e in plan["engines"].values())
+        return {(pk, b, l): e for pk, pl in self._plans.items() for (b, l), e in pl.engines.items()}
 
     def needs_idle(self, **options) -> bool:
         """Would a frame with these `infer` options have to wait for launches in flight?  Only a change of `strength` /
         `controlnet_scale` of a plan that is running does (its graphs read those constants); other prompts, sizes, step
         counts and batch sizes go beside what is running.  (dispatch.py's worker drains before such a frame.)"""
         try:
-            from .lcm import lcm_timesteps
-
-            o = dict(height=360, width=640, strength=0.4, steps=20, controlnet=False, ref=False, controlnet_scale=1, prompt=["pixar, cg"])
-            o.update(options)
-            n_eff = len(lcm_timesteps(float(o["strength"]), int(o["steps"])))
-            use_cn = False if self.is_xl else (bool(o["controlnet"]) if self.honor_controlnet_flag else True)
-            use_ref = bool(o["ref"]) and self.honor_ref_flag and not self.is_xl
-            if use_ref:
-                return bool(self._outstanding)  # (reference image upload + one frame per launch: keep it simple)
-            pk = (o["height"] - o["height"] % 8, o["width"] - o["width"] % 8, int(o["steps"]), n_eff, use_cn and not use_ref, use_ref)
-            if self.is_xl:
-                pk += (o["prompt"] if isinstance(o["prompt"], str) else tuple(o["prompt"]),)
-            if getattr(self, "device_seed", False):
-                pk += (_DEVICE_SEED,)
-            if getattr(self, "frame_prompts", False):
-                pk += (_FRAME_PROMPTS,)
-            if getattr(self, "frame_options", False) and not self.is_xl:
+            o = dict(INFER_DEFAULTS, **options)
+            key = self._plan_key(o)
+            if key.use_ref:
+                return bool(self._in_flight)  # (reference image upload + one frame per launch: keep it simple)
+            if key.frame_options:
                 return False  # (options are per frame slot of the lane's own engine: a new value never waits for another lane)
-            plan = self._plans.get(pk)
-            if plan is None:
-                return False
-            return plan["opts"] != (float(o["strength"]), float(o["controlnet_scale"])) and self._plan_busy(plan)
+            plan = self._plans.get(key)
+            return plan is not None and plan.opts != (float(o["strength"]), float(o["controlnet_scale"])) and plan.busy(self._in_flight)
         except Exception:
-            return bool(self._outstanding)
+            return bool(self._in_flight)
 
     def _engine_for(self, plan_key, opts, batch: int, lane: int = 0, prompt=None, prompt_text=None):
         """A prepared engine per (program, frames per launch, lane).  A program's first engine owns its schedule constants;
         the others are slots of it (shared weights and constants, own arena / prompt constants / graph), so that switching
         between batch sizes, lanes, prompts and PROGRAMS costs nothing per frame.  `opts` = (strength, controlnet_scale): a
         change rewrites that program's device constants, nothing else."""
-        height, width, steps, _n, use_cn, use_ref = plan_key[:6]
         strength, cn_scale = opts
-        frame_opts = _FRAME_OPTIONS in plan_key[6:]  # (options per frame slot of each engine: the plan has none, `opts` only seeds `prepare`)
+        frame_opts = plan_key.frame_options  # (options per frame slot of each engine: the plan has none, `opts` only seeds `prepare`)
         plan = self._plans.get(plan_key)
         if plan is not None:
             self._plans.move_to_end(plan_key)
-            if not frame_opts and opts != plan["opts"]:
-                if self._plan_busy(plan):
+            if not frame_opts and opts != plan.opts:
+                if plan.busy(self._in_flight):
                     raise RuntimeError("cannot change strength / controlnet_scale of a plan with launches in flight: collect them first")
                 t0 = time.perf_counter()
-                if not plan["root"].update_options(strength, cn_scale):  # (cannot happen: the timestep count is in the key)
+                if not plan.root.update_options(strength, cn_scale):  # (cannot happen: the timestep count is in the key)
                     raise RuntimeError("update_options refused a schedule with the same number of timesteps")
-                plan["opts"] = opts
+                plan.opts = opts
                 self._note("update_options", t0)
-            eng = plan["engines"].get((batch, lane))
+            eng = plan.engines.get((batch, lane))
             if eng is not None:
-                if eng in self._outstanding:
+                if any(h.engine is eng for h in self._in_flight):
                     raise RuntimeError("this lane's previous launch has not been collected")
                 return eng
         t0 = time.perf_counter()
@@ -697,31 +701,27 @@ class VideoSDPipeline:
             for pk in list(self._plans):
                 if len(self._plans) < max(1, self.max_plans):
                     break
-                if not self._plan_busy(self._plans[pk]):
-                    for e in self._plans.pop(pk)["engines"].values():
-                        e._destroy_graphs()
+                if not self._plans[pk].busy(self._in_flight):
+                    self._evict(pk)
             eng = self.model.make_slot(share_plan=False, lane=lane)  # its own schedule constants: the other programs keep running
-            plan = self._plans[plan_key] = {"root": eng, "opts": None if frame_opts else opts, "engines": {}}
+            plan = self._plans[plan_key] = _Plan(eng, None if frame_opts else opts)
         else:
-            eng = plan["root"].make_slot(lane=lane)
+            eng = plan.root.make_slot(lane=lane)
         if prompt is not None:
             eng.use_prompts(prompt) if isinstance(prompt, list) else eng.use_prompt(prompt)
         if self.is_xl:  # micro-conditioning: original size = target size = the frame size, no crop
-            eng.set_added_cond(self.encode_pooled(prompt_text if prompt_text is not None else ""), (height, width, 0, 0, height, width))
-        # (every engine is captured both ways -- ControlNet encoder on the lane's side stream / everything on the lane's own
-        #  stream; `submit_batch` picks per launch, see `_overlap_now`)
-        # Kernel choices: coalesced launches of a worker with three or four lanes are the loaded case -- the forms that cost least
-        # with four lanes busy; one-frame launches and workers with one or two lanes are the latency case -- the forms that are
-        # fastest alone.  Fixed per plan, the same on every lane (same bits whichever lane a frame lands on).
+            eng.set_added_cond(self.encode_pooled(prompt_text if prompt_text is not None else ""),
+                               (plan_key.height, plan_key.width, 0, 0, plan_key.height, plan_key.width))
+        # (every engine is captured both ways -- ControlNet encoder on the lane's side stream / everything on the lane's own stream;
+        #  `submit_batch` picks per launch, see `_overlap_now`)
+        # Kernel choices: coalesced launches of a worker with three or four lanes are the loaded case -- the forms that cost least with four
+        # lanes busy; one-frame launches and workers with one or two lanes are the latency case -- the forms that are fastest alone.  Fixed
+        # per plan, the same on every lane (same bits whichever lane a frame lands on).
         eng.tune_for_lanes = self.max_lanes >= 3 and batch > 1
-        mode = {"device_seed": True} if _DEVICE_SEED in plan_key[6:] else {}
-        if _FRAME_PROMPTS in plan_key[6:]:
-            mode["frame_prompts"] = True
-        if frame_opts:
-            mode["frame_options"] = True
-        eng.prepare(height, width, steps, strength, controlnet_scale=cn_scale, use_controlnet=use_cn, batch=batch, ref_mode=use_ref,
-                    autotune=self.tuning_mode != "table", **mode)
-        plan["engines"][(batch, lane)] = eng
+        mode = {k: True for k in ("device_seed", "frame_prompts", "frame_options") if getattr(plan_key, k)}  # (the default mode, and stand-ins: none)
+        eng.prepare(plan_key.height, plan_key.width, plan_key.steps, strength, controlnet_scale=cn_scale, use_controlnet=plan_key.use_cn,
+                    batch=batch, ref_mode=plan_key.use_ref, autotune=self.tuning_mode != "table", **mode)
+        plan.engines[(batch, lane)] = eng
         self._note("prepare", t0)
         return eng
 
@@ -729,11 +729,13 @@ class VideoSDPipeline:
         dev = int(self.device)
         used = torch.cuda.memory_allocated(dev)
         if before is not None and used >= before:  # an evicted engine still referenced from a cycle: collect it now
-            import gc
-
             gc.collect()
             used = torch.cuda.memory_allocated(dev)
         return used, self.memory_budget * torch.cuda.mem_get_info(dev)[1]
+
+    def _evict(self, key) -> int:
+        """drop the (idle) program `key` from the cache and release its engines' graphs -> how many engines went"""
+        return self._plans.pop(key).destroy()
 
     def _trim_memory(self, keep=None):
         """Before another engine (= another arena) is allocated: while the allocator holds more than the budget, drop idle
@@ -745,21 +747,18 @@ class VideoSDPipeline:
             return 0
         dropped = 0
         for pk in list(self._plans):
-            if pk == keep or self._plan_busy(self._plans[pk]):
+            if pk == keep or self._plans[pk].busy(self._in_flight):
                 continue
-            for e in self._plans.pop(pk)["engines"].values():
-                e._destroy_graphs()
-                dropped += 1
-            e = None
+            dropped += self._evict(pk)
             used = self._memory_used_and_limit(before=used)[0]
             if used <= limit:
                 break
         plan = self._plans.get(keep)
         if plan is not None and used > limit:
-            for k, e in list(plan["engines"].items()):
-                if e is plan["root"] or e in self._outstanding:
+            for k, e in list(plan.engines.items()):
+                if e is plan.root or any(h.engine is e for h in self._in_flight):
                     continue
-                del plan["engines"][k]
+                del plan.engines[k]
                 e._destroy_graphs()
                 dropped += 1
                 e = None
@@ -778,26 +777,25 @@ class VideoSDPipeline:
         `frames_per_launch` > 1: the coalesced program of `infer_batch`.  Returns the exporter's summary (videosd_amd/plan.py)."""
         from .plan import export_plan
 
-        if getattr(self, "frame_prompts", False):
+        if self.frame_prompts:
             raise ValueError("export_plan: this pipeline was built with frame_prompts=True; a plan file holds ONE prompt's constants and the C "
                              "library has no per-frame prompt entry point yet: export from a pipeline built without it")
-        if getattr(self, "frame_options", False):
+        if self.frame_options:
             raise ValueError("export_plan: this pipeline was built with frame_options=True; its programs call vsd_add_noise_frames, "
                              "vsd_lcm_step_frames, vsd_groupnorm_addvec and vsd_cn_merge_frames, which are not plan functions: export from a "
                              "pipeline built without it (a loaded plan follows the sliders through vsd_plan_set_options)")
         self._require_idle("export a plan")
-        w, h = int(options.get("width", 640)), int(options.get("height", 360))
+        w, h = int(options.get("width", INFER_DEFAULTS["width"])), int(options.get("height", INFER_DEFAULTS["height"]))
         imgs = [Image.new("RGB", (w, h), (127, 127, 127)) for _ in range(int(frames_per_launch))]
         handle = self.submit_batch(imgs, **options)
         self.collect_batch(handle)
-        return export_plan(handle[0], path)
+        return export_plan(handle.engine, path)
 
     def export_prompt(self, path: str, prompt) -> int:
         """Another prompt's constants as a file for vsd_plan_load_prompt (a loaded plan takes it without a new plan)."""
         from .plan import export_prompt
 
-        pkey = prompt if isinstance(prompt, str) else tuple(prompt)
-        return export_prompt(self._cache_prompt(pkey, prompt=prompt), path)
+        return export_prompt(self._cache_prompt(_prompt_key(prompt), prompt=prompt), path)
 
     def set_tuning_mode(self, mode: str):
         """ "auto" (time the candidates of shapes the table lacks at `prepare`) or "table" (never: deterministic heuristic)."""
@@ -836,3 +834,5 @@ class VideoSDPipeline:
 
 
 VideoPipeline = VideoSDPipeline  # BASELINE.json's north_star calls the class by this name
+# the defaults of `infer` (its three literal signatures mirror the reference's), for everything here that completes an option dict
+INFER_DEFAULTS = {k: v.default for k, v in inspect.signature(VideoSDPipeline.infer).parameters.items() if v.default is not v.empty}
