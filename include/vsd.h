@@ -52,7 +52,7 @@ enum vsd_family {
   VSD_FAM_ATTENTION = 4, VSD_FAM_ELEMENTWISE = 5, VSD_FAM_COUNT = 6
 };
 
-/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds; vsd_prompt_install joined version 10 without a bump: plan files do not change, and a library without the symbol is refused by name at load) and the size in
+/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds; vsd_prompt_install joined version 10 without a bump: plan files do not change, and a library without the symbol is refused by name at load; so did the three vsd_canny_* entry points) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
 #define VSD_VERSION 10
@@ -441,6 +441,38 @@ int vsd_rgb_to_i420(vsd_ctx* ctx, const void* rgb_u8, int h, int w, void* dst_y,
 int vsd_i420_to_rgb_host(const void* y, int64_t y_stride, const void* u, const void* v, int64_t uv_stride, int ox, int oy, int h, int w,
                          void* dst_rgb, int64_t dst_row_bytes);
 int vsd_rgb_to_i420_host(const void* rgb_u8, int h, int w, void* dst_y, void* dst_u, void* dst_v, int64_t y_stride, int64_t uv_stride);
+
+/* ---- Canny edges for the ControlNet, on the device (csrc/canny.hip, csrc/canny_core.h) ----------------------------------------------
+ * The ControlNet served here (control_v11p_sd15_canny) was trained on Canny maps: binary, one pixel wide, after non-maximum suppression
+ * and hysteresis.  The reference feeds it a Sobel magnitude instead (canny_gpu.py:27-44, kept as the default: vsd_sobel_control above);
+ * this is the opt-in alternative, with the same inputs and outputs.
+ * THE EDGE CONTRACT (fixed; integers only; device kernels, the host twin and the tests are held to it byte for byte):
+ *   gray value  L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16  (PIL convert("L"), as vsd_sobel_control forms it).
+ *   gradients   3 x 3 Sobel on L with the border replicated: dx = right column - left column, dy = bottom row - top row, weights 1, 2, 1.
+ *               magnitude m = |dx| + |dy|, 0..2040; the magnitude of a position outside the image is 0.
+ *   thresholds  integers, 0 <= low <= high <= 2040; anything else is VSD_ERR_ARG.
+ *   candidates  m > low and a maximum along the gradient.  With x = |dx|, y = |dy| << 15, t22 = x * 13573, t67 = t22 + (x << 16)
+ *               (x <= 1020: t67 <= 80 691 180 and y <= 33 423 360, below 2^31 -- 32-bit int arithmetic is exact):
+ *                 y < t22:   m > m(left) && m >= m(right)
+ *                 y > t67:   m > m(up) && m >= m(down)
+ *                 otherwise, s = ((dx ^ dy) < 0) ? -1 : 1:   m > m(row - 1, col - s) && m > m(row + 1, col + s)
+ *   strong      a candidate with m > high.
+ *   hysteresis  an edge is every candidate whose 8-connected component of candidates contains a strong candidate.
+ *   outputs     as vsd_sobel_control writes them: edge_u8 [h][w] = 255 or 0; control_out fp16 [h*w][8] = {v, v, v, 0, 0, 0, 0, 0} with
+ *               v = 1 or 0.  A constant frame gives no edges (and there is no division anywhere: no NaN).
+ *   This is the arithmetic OpenCV documents for Canny with aperture 3 and the L1 norm, restated.  It is NOT claimed to equal OpenCV's
+ *   bytes: how far cv2.Canny is from it is not measured anywhere in this tree (its tests run without OpenCV).
+ * vsd_canny_control: rgb_u8 packed [h][w][3], any alignment; control_out 16-byte aligned; sides 1..VSD_RESAMPLE_MAX_SIDE.  workspace:
+ *   >= vsd_canny_workspace_bytes(h, w) bytes, 4-byte aligned, its contents on entry do not matter; it carries the labels between the
+ *   call's launches, so two calls in flight at once need a workspace each.  Always four launches on `stream`, whatever the frame holds:
+ *   no memset, no host synchronisation, no cooperative launch; capturable.  The result is a function of the frame alone, bit for bit
+ *   the same on every run.
+ * vsd_canny_host: the contract as plain host loops with a stack flood fill; no GPU and no context (VSD_ERR_ARG without a message).
+ * Not a plan function: a program that records it has no plan-file export. */
+int64_t vsd_canny_workspace_bytes(int h, int w);
+int vsd_canny_control(vsd_ctx* ctx, const void* rgb_u8, int h, int w, int low, int high, void* edge_u8, void* control_out, void* workspace,
+                      void* stream);
+int vsd_canny_host(const void* rgb_u8, int h, int w, int low, int high, void* edge_u8);
 
 /* ---- two independent operations as ONE grid per kernel ------------------------------------------------
  * The reference runs the ControlNet and then the UNet encoder of a denoising step -- the same topology with two weight sets on the

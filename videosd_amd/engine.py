@@ -179,7 +179,9 @@ class Engine:
         self.buffers = None          # name -> the program's persistent tensors (latents, eps, ...), for tests and probes
         self.frame_u8 = None         # the launch's input frame(s)
         self.out_u8 = None           # ... its output frame(s)
-        self.edge_u8 = None          # ... its Sobel edge map(s)
+        self.edge_u8 = None          # ... its edge map(s)
+        self.edges = None            # what `edge_u8` and the ControlNet's conditioning hold: "sobel" (the reference's stand-in) or "canny"
+        self.canny_thresholds = None  # `edges="canny"`: (low, high), integers on |dx| + |dy|
         self.ref_u8 = None           # `ref_mode`: the reference image
         self._ref_epoch = None       # ... and which reference image of the pipeline `ref_u8` holds (VideoSDPipeline sets it)
         self.noise = None            # the host draws on the device (None: `device_seed`)
@@ -968,7 +970,8 @@ class Engine:
 
     def prepare(self, H: int, W: int, steps: int, strength: float, controlnet_scale: float = 1.0,
                 use_controlnet: bool = True, use_graph: Optional[bool] = None, autotune: bool = True, batch: int = 1,
-                ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False, frame_options: bool = False):
+                ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False, frame_options: bool = False,
+                edges: str = "sobel", canny_thresholds=(100, 200)):
         """Fix the frame geometry and schedule; build the static program and capture it into a hipGraph
         (the reference's intent at videopipeline.py:35-47, `compile_model`).
 
@@ -998,7 +1001,17 @@ class Engine:
         the scheduler ops are the `_frames` forms, conv1 of every ResnetBlock is recorded without its time vector and norm2 adds the
         frame's slice of the time table to its input (`groupnorm_addvec`), the zero-convs are recorded without scale and residual and one
         `cn_merge_frames` launch per step merges all 13 residuals with the frame's scales.  Composes with device_seed and frame_prompts;
-        not with ref_mode or an SDXL UNet.  Default: one set of options per plan (`update_options`), as before."""
+        not with ref_mode or an SDXL UNet.  Default: one set of options per plan (`update_options`), as before.
+
+        edges: what the ControlNet is conditioned on.  "sobel" (default): the reference's stand-in, the Sobel magnitude over the frame's
+        maximum (canny_gpu.py:27-44).  "canny": real Canny edges by THE EDGE CONTRACT of include/vsd.h -- binary, one pixel wide, what
+        control_v11p_sd15_canny was trained on; the program records `canny_control` in place of `sobel_control`, call for call.
+        canny_thresholds = (low, high): integers with 0 <= low <= high <= 2040 on |dx| + |dy| (floats are floored), read by "canny" only.
+        Composes with every other mode (none of them touches the edge stage); without a ControlNet there is no edge stage and the
+        switch is inert.  A "canny" program has no plan-file export (`vsd_canny_control` is not a plan function)."""
+        edges, canny_thresholds = L.check_edges(edges, canny_thresholds)
+        if edges == "canny" and not hasattr(self.ops, "canny_control"):
+            raise ValueError('edges="canny" needs the op canny_control, which this ops object does not have')
         self._check_arguments(H, W, batch, use_controlnet, ref_mode, device_seed, frame_prompts, frame_options)
         sched = LCMSchedule(strength, steps)
         self._prepare_prompt_block(batch, frame_prompts)
@@ -1007,6 +1020,7 @@ class Engine:
         self._reset_plan_state()
         self.batch = batch
         self.frame_prompts, self.frame_options = bool(frame_prompts), bool(frame_options)
+        self.edges, self.canny_thresholds = edges, canny_thresholds if edges == "canny" else None
         # The lock-step encoders are the one-stream form of EVERY program.  What a pair's grid looks like depends on the mode: a one-frame
         # program (latency mode) takes the pair's own table entry, timed alone; a coalesced launch on busy lanes (throughput mode) runs
         # the pair in the form its members have as launches of their own -- a latency-chosen form there occupies more workgroup-time
@@ -1022,6 +1036,7 @@ class Engine:
         self._record(sched, sops, coef, H, W, use_controlnet, ref_mode)
         self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=len(sched), batch=batch,
                          ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), frame_options=bool(frame_options), tuned_for_lanes=bool(self.tune_for_lanes),
+                         edge_mode=self.edges, canny_thresholds=self.canny_thresholds,  # ("edges" is taken: the event edges of the captured sequence)
                          sizes=self._level_sizes(H, W), timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=self.arena.peak)
         self._warm_up_and_capture(autotune)
         return self.plan
@@ -1161,7 +1176,10 @@ class Engine:
                 r.fork()
                 r.use_stream(1)
             for b in range(B):  # the edge map is normalised by ITS frame's maximum (canny_gpu.py:39)
-                r.sobel_control(frame_b[b], H, W, 0.11, 0.8, img(self.edge_u8, b, H * W), img(ctrl, b, H * W))  # videopipeline.py:109
+                if self.edges == "canny":
+                    r.canny_control(frame_b[b], H, W, *self.canny_thresholds, img(self.edge_u8, b, H * W), img(ctrl, b, H * W))
+                else:
+                    r.sobel_control(frame_b[b], H, W, 0.11, 0.8, img(self.edge_u8, b, H * W), img(ctrl, b, H * W))  # videopipeline.py:109
             cond_emb = self._cond_embedding(r, ctrl, H, W)
             self.buffers["control"], self.buffers["cond_emb"] = ctrl, cond_emb
             if side0:

@@ -1,6 +1,7 @@
 """ctypes binding of libvsd.so (include/vsd.h).  No fallback: if the HIP library is missing or a call
 fails, a RuntimeError is raised."""
 import ctypes as C
+import math
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -19,6 +20,23 @@ TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128, TILE_256x128, TILE_256x64, T
 TILE_DIMS = {TILE_128x128: (128, 128), TILE_128x64: (128, 64), TILE_64x64: (64, 64), TILE_64x128: (64, 128),
              TILE_256x128: (256, 128), TILE_256x64: (256, 64), TILE_256x256: (256, 256)}
 FAMILIES = ["conv_gemm", "splitk_reduce", "groupnorm", "layernorm", "attention", "elementwise"]
+EDGE_MODES = ("sobel", "canny")  # what the ControlNet is conditioned on: vsd_sobel_control (the reference's stand-in) / vsd_canny_control
+CANNY_MAX_MAG = 2040  # include/vsd.h THE EDGE CONTRACT: |dx| + |dy| of a 3 x 3 Sobel on 8-bit gray values
+
+
+def check_edges(edges, canny_thresholds):
+    """-> (edges, (low, high)) as `Engine.prepare` and `VideoSDPipeline` take them, checked against THE EDGE CONTRACT of include/vsd.h:
+    `edges` one of EDGE_MODES; the thresholds two numbers, floored to integers, with 0 <= low <= high <= CANNY_MAX_MAG."""
+    if edges not in EDGE_MODES:
+        raise ValueError(f'edges must be "sobel" or "canny", not {edges!r}')
+    try:
+        low, high = canny_thresholds
+        low, high = math.floor(low), math.floor(high)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"canny_thresholds must be two numbers (low, high), not {canny_thresholds!r}") from None
+    if not 0 <= low <= high <= CANNY_MAX_MAG:
+        raise ValueError(f"canny_thresholds must satisfy 0 <= low <= high <= {CANNY_MAX_MAG} (integers on |dx| + |dy|), not {canny_thresholds!r}")
+    return edges, (int(low), int(high))
 
 
 class ConvDesc(C.Structure):
@@ -119,6 +137,9 @@ SIGNATURES = {
     "vsd_rgb_to_i420": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "vsd_i420_to_rgb_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "vsd_rgb_to_i420_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    "vsd_canny_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "vsd_canny_control": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vsd_canny_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vsd_graph_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vsd_graph_end": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "vsd_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

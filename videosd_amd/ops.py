@@ -976,6 +976,15 @@ class HipOps:
         self.ctx.call("vsd_sobel_control", self._p(rgb_u8), h, w, low, high, self._p(edge_u8), self._p(control_out),
                       self._p(ws), self.s)
 
+    def canny_control(self, rgb_u8, h, w, low, high, edge_u8, control_out):
+        """Canny edges by THE EDGE CONTRACT of include/vsd.h (csrc/canny.hip): the same inputs and outputs as `sobel_control`, integer
+        thresholds on |dx| + |dy| (0..2040).  The workspace carries the labels between the call's four launches: it is this object's,
+        keyed like "sobel" by the scratch set of the stream in use -- objects are per launch lane (`clone`), so two lanes never share it,
+        and the calls of one object on one stream run one after the other."""
+        ws = self.workspace("canny", int(self.ctx.lib.vsd_canny_workspace_bytes(h, w)))
+        self.ctx.call("vsd_canny_control", self._p(rgb_u8), int(h), int(w), int(low), int(high), self._p(edge_u8), self._p(control_out),
+                      self._p(ws), self.s)
+
     def add_noise(self, x0, noise_f32, sqrt_a, sqrt_b, hw, out):
         self.ctx.call("vsd_add_noise", self._p(x0), self._p(noise_f32), sqrt_a, sqrt_b, hw, self._p(out), self.s)
 

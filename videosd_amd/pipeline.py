@@ -27,7 +27,7 @@ from . import checkpoints as CK
 from . import weights as W
 from .frames import I420Frame, is_i420
 from .lcm import lcm_timesteps
-from .lib import RESAMPLE_MAX_SIDE
+from .lib import RESAMPLE_MAX_SIDE, check_edges
 
 
 def center_crop_resize(img: Image.Image, width: int, height: int) -> Image.Image:
@@ -149,6 +149,13 @@ class VideoSDPipeline:
             frame slot ahead of the launch, so nothing is drained.  Off: one pair per plan (`Engine.update_options`).  SDXL and
             reference-only programs keep the default form either way.
         The last three are modes of `Engine.prepare`; a worker coalesces frames that differ in what they make per-frame (`per_frame_*`).
+        edges="canny", canny_thresholds=(100, 200): the ControlNet is conditioned on real Canny edges, computed on the device by THE EDGE
+            CONTRACT of include/vsd.h (gray value, 3 x 3 Sobel, |dx| + |dy|, non-maximum suppression, hysteresis: binary and one pixel wide,
+            what control_v11p_sd15_canny was trained on).  The thresholds are integers on |dx| + |dy|, 0 <= low <= high <= 2040 (floats are
+            floored).  The arithmetic is the one OpenCV documents for Canny(aperture 3, L1 norm); equality with cv2's bytes is not measured.
+            Default edges="sobel": the reference's stand-in (canny_gpu.py:27-44), the same programs and bits as before.  Fixed for the life
+            of the object; composes with every switch above; such a pipeline has no `export_plan`.  SDXL has no ControlNet tower: there
+            the switch is accepted and inert.
         lanes: launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on launch
             stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch.
         tuning_mode: "auto": shapes missing from the table are timed on this GPU at `prepare`; "table": never -- they take the deterministic
@@ -164,6 +171,7 @@ class VideoSDPipeline:
         self.device = kwargs.get("device", 0)
         for switch in ("honor_controlnet_flag", "honor_ref_flag", "device_resize", "device_seed", "frame_prompts", "frame_options"):
             setattr(self, switch, bool(kwargs.get(switch, False)))
+        self.edges, self.canny_thresholds = check_edges(kwargs.get("edges", "sobel"), kwargs.get("canny_thresholds", (100, 200)))
         self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
         self.tuning_mode = str(kwargs.get("tuning_mode", "auto"))
         self.max_prompts = int(kwargs.get("max_prompts", 8))
@@ -719,6 +727,8 @@ class VideoSDPipeline:
         # per plan, the same on every lane (same bits whichever lane a frame lands on).
         eng.tune_for_lanes = self.max_lanes >= 3 and batch > 1
         mode = {k: True for k in ("device_seed", "frame_prompts", "frame_options") if getattr(plan_key, k)}  # (the default mode, and stand-ins: none)
+        if self.edges != "sobel":  # (not in the plan key: constant for the life of this object)
+            mode.update(edges=self.edges, canny_thresholds=self.canny_thresholds)
         eng.prepare(plan_key.height, plan_key.width, plan_key.steps, strength, controlnet_scale=cn_scale, use_controlnet=plan_key.use_cn,
                     batch=batch, ref_mode=plan_key.use_ref, autotune=self.tuning_mode != "table", **mode)
         plan.engines[(batch, lane)] = eng
@@ -784,6 +794,9 @@ class VideoSDPipeline:
             raise ValueError("export_plan: this pipeline was built with frame_options=True; its programs call vsd_add_noise_frames, "
                              "vsd_lcm_step_frames, vsd_groupnorm_addvec and vsd_cn_merge_frames, which are not plan functions: export from a "
                              "pipeline built without it (a loaded plan follows the sliders through vsd_plan_set_options)")
+        if self.edges != "sobel":
+            raise ValueError(f'export_plan: this pipeline was built with edges="{self.edges}"; its programs call vsd_canny_control, which is not a '
+                             'plan function: export from a pipeline built with edges="sobel" (the default)')
         self._require_idle("export a plan")
         w, h = int(options.get("width", INFER_DEFAULTS["width"])), int(options.get("height", INFER_DEFAULTS["height"]))
         imgs = [Image.new("RGB", (w, h), (127, 127, 127)) for _ in range(int(frames_per_launch))]

@@ -235,6 +235,9 @@ def export_plan(engine, path: str) -> dict:
         raise ValueError("export_plan: this engine was prepared with frame_options=True; its program calls vsd_add_noise_frames, vsd_lcm_step_frames, "
                          "vsd_groupnorm_addvec and vsd_cn_merge_frames, which are not plan functions: export the plan of an engine prepared "
                          "without it (a loaded plan follows strength / ControlNet scale through vsd_plan_set_options)")
+    if engine.plan.get("edge_mode", "sobel") != "sobel":
+        raise ValueError(f'export_plan: this engine was prepared with edges="{engine.plan["edge_mode"]}"; its program calls vsd_canny_control, which is not a '
+                         'plan function: export the plan of an engine prepared with edges="sobel" (the default)')
     ops.synchronize()
     calls = []
 
