@@ -74,8 +74,8 @@ def stream(w, imgs, pairs):
 
 def device_costs():
     """(c) and the zero-convs' kernel forms, on an engine of the real networks in this process"""
+    from videosd_amd import convform as CF
     from videosd_amd import lib as L
-    from videosd_amd.ops import choose_tile
     from videosd_amd.pipeline import PlanKey
 
     p = VideoSDPipeline(frame_options=True, tuning_mode="table", lanes=LANES, **MODEL)
@@ -87,14 +87,14 @@ def device_costs():
     for fn, a, k in eng.program.calls:
         if fn.__name__ == "conv_group" and all(not kk for _aa, kk in a[0]) and all(aa[3].ksize == 1 for aa, _kk in a[0]):
             gkey = ops.group_key(a[0], k.get("split"))
-            gent = ops.tile_override.get(gkey)
+            gent = CF.lookup(ops.tile_override, gkey)
             seen[("group of %d zero-convs" % len(a[0]),)] = "table entry %s" % (gent,) if gent is not None else "no table entry: the group's default form"
             for aa, kk in a[0]:
                 key = ops.conv_key_of(aa[2], aa[3], kk)
-                ent = ops.tile_override.get(key)
-                t, sp = choose_tile(aa[2].m, aa[3].n, aa[3].kp)
-                seen[key[:3]] = (f"table entry (tile {tile_name.get(ent[0], ent[0])}, split_k {ent[1]})" if ent is not None else
-                                 f"no table entry: choose_tile -> {tile_name.get(t, t)}, split_k {sp}")
+                ent = CF.lookup(ops.tile_override, key)
+                f = CF.resolve(CF.conv_call(aa[2], aa[3], **kk), ops.tile_override, ops.tune_mode, CF.flags_of(ops))
+                seen[key[:3]] = (("table entry" if ent is not None else "no table entry: choose_tile ->") +
+                                 f" (tile {tile_name.get(f.tile, f.tile)}, split_k {f.split_k})")
     say("zero-convs of the frame_options program (M, N, Kp) at 5 frames per launch, throughput-mode table:")
     for key, what in seen.items():
         say(f"  {key}: {what}")

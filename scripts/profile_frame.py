@@ -5,9 +5,9 @@ the table's mode-1 entries -- larger tiles, the halo form, the eight-wave forms)
 import json, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from videosd_amd import config as C, weights as W, lib as L
+from videosd_amd import config as C, convform as CF, weights as W, lib as L
 from videosd_amd.engine import Engine
-from videosd_amd.ops import HipOps, choose_tile
+from videosd_amd.ops import HipOps
 
 cn = "--no-cn" not in sys.argv
 size = 512
@@ -34,15 +34,8 @@ meta = []
 
 def conv_meta(a, k):
     g, w = a[2], a[3]
-    tile, split = k.get("tile"), k.get("split_k")
-    if tile is None:
-        tile, sk = choose_tile(g.m, w.n, w.kp, w.geglu, k.get("t_col0", 0) if k.get("out_t") is not None else 0)
-        split = sk if split is None else split
-    key = ops.conv_key_of(g, w, k)
-    ink = True
-    if k.get("tile") is None and key in ops.tile_override:
-        tile, split, ink, _pl = ops.tile_override[key]
-    split = split or 1
+    # (the form that runs: the table entry with its mode fallback, else the heuristic, then the safety nets)
+    tile, split, ink, _pl = CF.resolve(CF.conv_call(g, w, **k), ops.tile_override, ops.tune_mode, CF.flags_of(ops), **CF.named_form(k))
     kt = w.kp // 64
     split = min(split, kt); per = -(-kt // split); split = -(-kt // per)
     return dict(op="conv", M=g.m, N=w.n, K=w.k, ks=g.ksize, stride=g.stride, resize=(g.hi != g.hs), tile=tile, split=split if not ink else -split,
@@ -57,7 +50,7 @@ for fn, a, k in eng.program.calls:
     if name == "conv":
         m = conv_meta(a, k)
     elif name == "conv_group":  # several independent convs in one grid (the ControlNet merges): one kernel, the members' sums
-        ent = ops.tile_override.get(ops.group_key(a[0], k.get("split")))
+        ent = CF.lookup(ops.tile_override, ops.group_key(a[0], k.get("split")))
         if ent is not None and ent[0] == ops.GROUP_ALONE:  # (the table sends this group's members out as launches of their own)
             meta.extend(conv_meta(aa, kk) for aa, kk in a[0])
             continue

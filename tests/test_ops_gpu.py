@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import exact_cases as X
+from videosd_amd.convform import conv_call
 
 pytestmark = pytest.mark.gpu
 
@@ -435,7 +436,7 @@ def test_twin_convs_split_over_k_share_a_grid_and_a_reducer(ops):
     key = ops.conv_key_of(members[0][0][2], members[0][0][3], members[0][1])
     saved = ops.tile_override.get(key)
     ops.tile_override[key] = (L.TILE_128x64, 1, True, 7)
-    halo_ok = ops._halo_call_ok(members[0][0][2], members[0][0][3], 0, 0, 1.0, None, None, None, None, None, None)
+    halo_ok = conv_call(members[0][0][2], members[0][0][3]).halo_ok
     assert (ops.pair_split(*members[0], *members[1]) is None) == halo_ok
     if saved is None:
         del ops.tile_override[key]

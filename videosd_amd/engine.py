@@ -28,6 +28,7 @@ from . import lib as L
 from .blocks import (FRAME_OPTION_OPS, MAX_OPTION_ENTRIES, FramePromptLayout, FrameSlots, OptionEntry, OptionLayout,  # noqa: F401
                      PromptBlock, PromptLayout, controlnet_scales, option_segments, prompt_segments, schedule_constants)
 from .config import ControlNetConfig, TAESDConfig, UNetConfig
+from .convform import OWN_SPLIT, lookup
 from .lcm import LCMSchedule, timestep_sinusoid, w_embedding
 from .netweights import XATTN_ABSORB_MIN_C, BlockW, NetWeights, ResnetW, TAESDWeights, TransformerW  # noqa: F401
 from .ops import Geom
@@ -915,30 +916,28 @@ class Engine:
         seen = {}
         # throughput-mode plans: candidates are timed with four lanes busy only offline / on request (ops.tune_lanes_online);
         # otherwise a shape without a throughput-mode entry takes its alone-timed choice, timed now if that is missing too
-        mode = getattr(ops, "tune_mode", 0)
-        online = mode == 0 or getattr(ops, "tune_lanes_online", False)
+        mode = ops.tune_mode  # (an ops object that tunes is HipOps: no probing past this point)
+        online = mode == 0 or ops.tune_lanes_online
         try:
             # the two-stream form first: a twin pair of the one-stream form runs at the split its members have as launches of their own
             calls = self.program.calls + (self.program_serial.calls if self.program_serial is not self.program else [])
             for fn, a, k in calls:
-                if fn.__name__ in ("conv_group", "pair") and hasattr(ops, "tune_group"):
+                if fn.__name__ in ("conv_group", "pair"):
                     ops.tune_mode = mode if online else 0  # (a group's form is timed alone either way; see ops.tune_group)
                     members, split = a[0], k.get("split")
-                    if split == getattr(ops, "OWN_SPLIT", None):  # (members at their own splits: their own forms first)
-                        for aa, kk in members:
-                            mk = ops.conv_key_of(aa[2], aa[3], kk)
-                            if mk not in ops.tile_override and kk.get("tile") is None:
-                                seen[mk] = ops.tune_conv(aa, kk)[0]
                     if fn.__name__ == "pair":
                         if a[0][0].__name__ != "conv" or a[1][0].__name__ != "conv":
                             continue
                         if mode == 1:  # (throughput mode: a pair runs in its members' own form, ops.pair -- nothing to time)
                             continue
                         members = [(a[0][1], a[0][2]), (a[1][1], a[1][2])]
-                        for aa, kk in members:  # (a pair the one-stream form alone holds: its members' own forms first)
+                    if fn.__name__ == "pair" or split == OWN_SPLIT:
+                        # (members at their own splits, a pair the one-stream form alone holds: the members' own forms first)
+                        for aa, kk in members:
                             mk = ops.conv_key_of(aa[2], aa[3], kk)
                             if mk not in ops.tile_override and kk.get("tile") is None:
                                 seen[mk] = ops.tune_conv(aa, kk)[0]
+                    if fn.__name__ == "pair":
                         split = ops.pair_split(*members[0], *members[1])
                         if split is None:
                             continue
@@ -952,20 +951,18 @@ class Engine:
                     continue
                 ops.tune_mode = mode
                 key = ops.conv_key_of(a[2], a[3], k)
-                if key in seen or key in ops.tile_override or k.get("tile") is not None:
+                if k.get("tile") is not None or (ops.tile_override.get(key) if online else lookup(ops.tile_override, key)) is not None:
                     continue
-                if not online:
-                    ops.tune_mode = 0
-                    key = ops.conv_key_of(a[2], a[3], k)
-                    if key in seen or key in ops.tile_override:
-                        continue
+                if not online:  # (the alone-timed choice, which a throughput-mode key without an entry takes)
+                    ops.tune_mode, key = 0, key[:-1] + (0,)
+                if key in seen:
+                    continue
                 best, table = ops.tune_conv(a, k)
                 seen[key] = best
                 if verbose:
                     print("tune", key, "->", best, flush=True)
         finally:
-            if hasattr(ops, "tune_mode"):
-                ops.tune_mode = mode
+            ops.tune_mode = mode
         return seen
 
     def prepare(self, H: int, W: int, steps: int, strength: float, controlnet_scale: float = 1.0,

@@ -4,14 +4,17 @@ Tensors are torch CUDA(ROCm) tensors used purely as device buffers (`.data_ptr()
 call goes through the C-ABI of include/vsd.h on `self.stream`.
 """
 import ctypes as C
-import math
+import json
 import time
 from dataclasses import dataclass
+from functools import partial
 from typing import Optional
 
 import torch
 
+from . import convform as CF
 from . import lib as L
+from .convform import choose_tile  # noqa: F401  (scripts import it from here)
 from .packing import PackedConv
 
 import os as _os
@@ -50,32 +53,6 @@ class Geom:
     @property
     def m(self) -> int:
         return self.batch * self.ho * self.wo
-
-
-def choose_tile(m: int, n: int, kp: int, geglu: bool = False, t_col0: int = 0):
-    """Heuristic (tile, split_k): minimise padding waste, prefer big tiles, then split K until the grid
-    covers the 256 CUs.  The engine's autotuner can override this per layer."""
-    cands = [L.TILE_128x128, L.TILE_64x128] if geglu else [L.TILE_128x128, L.TILE_128x64, L.TILE_64x128, L.TILE_64x64]
-    pen = {L.TILE_128x128: 1.0, L.TILE_128x64: 1.12, L.TILE_64x128: 1.12, L.TILE_64x64: 1.3}
-    kt = kp // 64
-    best = None
-    for t in cands:
-        bm, bn = L.TILE_DIMS[t]
-        if t_col0 % bn:
-            continue
-        tm, tn = -(-m // bm), -(-n // bn)
-        blocks = tm * tn
-        waste = (tm * bm * tn * bn) / float(m * n)
-        split = 1
-        if not geglu and blocks < 256 and kt >= 8:
-            split = max(1, min(-(-320 // blocks), kt // 4))
-        total = blocks * split
-        fill = min(1.0, total / 256.0)
-        # rounds of 256-CU waves at ~2 blocks/CU
-        cost = waste * pen[t] / max(fill, 0.05) * (1.0 + 0.04 * (split - 1))
-        if best is None or cost < best[0]:
-            best = (cost, t, split)
-    return best[1], best[2]
 
 
 class LaneBook:
@@ -143,7 +120,6 @@ class HipOps:
             torch.cuda.set_stream(self.stream)
         self.device_id = device_id
         self._sidx = 0
-        self._pair_default = None
         self._widx = None  # scratch set of the call being issued when it is not the stream's own (members of a pair / group)
         self._events = {}
         self._ws = {}
@@ -344,40 +320,18 @@ class HipOps:
     def conv(self, src0, src1, g: Geom, w: PackedConv, out, *, ldo=None, c0=None, c1=0, rowvec=None, residual=None,
              residual2=None, ldr=None, out_scale=1.0, act=L.ACT_NONE, out2=None, add2=None, out_t=None, ldt=0,
              t_col0=0, tile=None, split_k=None, workspace=None, pipeline=None, rowstat_out=None, ln_part=None,
-             ln_eps=1e-5, chanstat_out=None, t_img=0, out_scale_dev=None, softmax_cols=0, _desc_only=False):
+             ln_eps=1e-5, chanstat_out=None, t_img=0, out_scale_dev=None, softmax_cols=0, inkernel=None, _desc_only=False):
         """t_img: with g.batch > 1, columns of out_t per image (image b's pixels start at column b * t_img).
-        out_scale_dev: one fp32 in device memory that replaces out_scale at run time (changeable under a captured graph)."""
+        out_scale_dev: one fp32 in device memory that replaces out_scale at run time (changeable under a captured graph).
+        tile / split_k / pipeline / inkernel (None: `self.inkernel_splitk`): the form where the caller names it, else convform.resolve's."""
         m = g.m
         c0 = c0 if c0 is not None else (w.cin - c1)
-        if w.geglu:
-            act = L.ACT_GEGLU
-        key = self.conv_key(g, w, t_col0, self.epilogue_class(w, rowstat_out, ln_part, chanstat_out, residual2, out2, out_scale_dev, out_scale, act))
-        inkernel = self.inkernel_splitk
-        if tile is None:
-            if key not in self.tile_override and key[-1] == 1 and key[:-1] + (0,) in self.tile_override:
-                key = key[:-1] + (0,)  # (no throughput-mode entry for this shape: the alone-timed choice)
-            if key in self.tile_override:
-                # (the key names the epilogue class since round 4: an entry always fits the call it is looked up for -- rounds
-                #  2-3 keyed on the shape alone and widened 64-column tiles / left the halo form after the fact)
-                tile, split_k, inkernel, pipeline = self.tile_override[key]
-            else:
-                tile, sk = choose_tile(m, w.n, w.kp, w.geglu or w.tile128, t_col0 if out_t is not None else 0)
-                split_k = sk if split_k is None else split_k
-        split_k = split_k or 1
-        if w.tile128:
-            inkernel = True  # (the tile softmax runs in the reducing workgroup's epilogue)
-        if pipeline == 10 and (self.no_c64 or out_scale_dev is not None or
-                               not self._c64_call_ok(g, w, c1, act, out_scale, residual, residual2, out2, out_t, rowstat_out, chanstat_out, ln_part,
-                                                     ldo if ldo is not None else w.n_out)):
-            # (safety net, as below: an entry shared by a call the persistent form cannot take)
-            pipeline, tile, split_k = (7, L.TILE_256x64, 1) if w.n % 8 == 0 else (3, L.TILE_64x64, 1)
-        if pipeline == 7 and (self.no_halo or out_scale_dev is not None or
-                              not self._halo_call_ok(g, w, c1, act, out_scale, residual2, out2, out_t, rowstat_out,
-                                                     chanstat_out, ln_part)):
-            # (safety net: a plain-class entry shared by a call the halo form cannot take -- e.g. SiLU after the residual)
-            pipeline = 3
-            tile = {L.TILE_256x128: L.TILE_128x128, L.TILE_256x64: L.TILE_128x64}.get(tile, tile)
-            inkernel = True
+        call = CF.conv_call(g, w, c1=c1, act=act, out_scale=out_scale, ldo=ldo, t_col0=t_col0, residual=residual, residual2=residual2,
+                            out2=out2, out_t=out_t, rowstat_out=rowstat_out, chanstat_out=chanstat_out, ln_part=ln_part,
+                            out_scale_dev=out_scale_dev)
+        act = call.act  # (GEGLU weights: the GEGLU epilogue)
+        tile, split_k, inkernel, pipeline = CF.resolve(call, self.tile_override, self.tune_mode, CF.flags_of(self), tile, split_k, pipeline,
+                                                       self.inkernel_splitk if inkernel is None else inkernel)
         d = L.ConvDesc()
         d.src0, d.src1 = self._p(src0), self._p(src1)
         d.c0, d.c1 = c0, c1
@@ -404,12 +358,11 @@ class HipOps:
         d.softmax_cols = softmax_cols
         d.act = act
         d.out = self._p(out)
-        d.ldo = ldo if ldo is not None else w.n_out
+        d.ldo = call.ldo
         d.out2, d.add2 = self._p(out2), self._p(add2)
         d.out_t, d.ldt, d.t_col0 = self._p(out_t), ldt, t_col0
         d.batch, d.t_img = g.batch, t_img
-        d.tile, d.split_k = tile, split_k
-        d.pipeline = self.default_pipeline if pipeline is None else pipeline
+        d.tile, d.split_k, d.pipeline = tile, split_k, pipeline
         if split_k > 1:
             ws = workspace if workspace is not None else self.workspace("splitk", split_k * m * w.n * 4)
             d.workspace = self._p(ws)
@@ -422,31 +375,19 @@ class HipOps:
         self.ctx.call("vsd_conv_gemm", C.byref(d), self.s)
 
     # ---- several independent convs as ONE launch (include/vsd.h vsd_conv_gemm_group)
-    GROUP_FORMS = [(L.TILE_64x64, 3), (L.TILE_64x64, 5), (L.TILE_64x128, 3), (L.TILE_64x128, 5), (L.TILE_128x64, 3), (L.TILE_128x64, 5),
-                   (L.TILE_128x128, 3), (L.TILE_128x128, 5), (L.TILE_128x128, 8), (L.TILE_128x128, 9)]
-    GROUP_ALONE = -1  # tile field of a group's table entry: "these members are faster as launches of their own"
-    OWN_SPLIT = "own"  # conv_group(split=...): every member at the split ITS OWN table entry has (split field 0 in the group's entry)
+    GROUP_FORMS, GROUP_ALONE, OWN_SPLIT = CF.GROUP_FORMS, CF.GROUP_ALONE, CF.OWN_SPLIT  # (see there)
+
+    def _policy(self):  # (what convform's functions take after the calls: the table, the tuning mode, the development switches)
+        return self.tile_override, self.tune_mode, CF.flags_of(self)
 
     def own_splits(self, calls):
-        """the split over K each member has as a launch of its own (its table entry / default form), or None when a member's own
-        form sums over K in another order than the buffer-load ring does (the halo-patch form, the 256-row tiles' callers keep
-        their form) -- then the group's bits would differ from the launches' and the members go out alone"""
-        out = []
-        for a, kw in calls:
-            kw = {k: v for k, v in kw.items() if k not in ("tile", "split_k", "pipeline")}
-            d = self.conv(*a, _desc_only=True, **kw)
-            if d.pipeline == 7 or d.tile in (L.TILE_256x128, L.TILE_256x64, L.TILE_256x256):
-                return None
-            out.append(int(d.split_k))
-        return out
+        return CF.own_splits(calls, *self._policy())
 
     def group_key(self, calls, split=None):
-        k = ["group"]
-        for a, kw in calls:
-            k += [a[2].m, a[3].n, a[3].kp]
-        if split is not None:  # (a twin pair: the members' own split over K is part of the problem, see `pair`; "own": OWN_SPLIT)
-            k += ["split", 0 if split == self.OWN_SPLIT else int(split)]
-        return tuple(k) + (int(self.tune_mode),)
+        return CF.group_key(calls, split, self.tune_mode)
+
+    def group_candidates(self, calls, split=None):
+        return CF.group_candidates(calls, *self._policy(), split=split)
 
     def conv_group(self, calls, form=None, split=None, default=None):
         """calls: [(args, kwargs), ...] as for `conv` (1 x 1 / 3 x 3 layers on the buffer-load path): ONE launch for all of them
@@ -464,11 +405,9 @@ class HipOps:
         if split == self.OWN_SPLIT:
             own = self.own_splits(calls)
             if own is None:
-                form = (self.GROUP_ALONE, 1, True, 0)
+                form = CF.ALONE
         if form is None:
-            ent = self.tile_override.get(self.group_key(calls, split))
-            if ent is None and self.tune_mode == 1:
-                ent = self.tile_override.get(self.group_key(calls, split)[:-1] + (0,))
+            ent = CF.lookup(self.tile_override, self.group_key(calls, split))
             form = ent if ent is not None else (default or (L.TILE_64x64, (0 if own else split) or 1, True, 3))
         tile, split_k, inkernel, pipeline = form
         if tile == self.GROUP_ALONE:
@@ -476,61 +415,50 @@ class HipOps:
                 self.conv(*a, **kw)
             return
         descs = (L.ConvDesc * len(calls))()
-        saved = self.inkernel_splitk
-        self.inkernel_splitk = bool(inkernel)
         try:
             for i, (a, kw) in enumerate(calls):
-                kw = {k: v for k, v in kw.items() if k not in ("tile", "split_k", "pipeline")}
                 # scratch set of member i on stream s: 2 i + s -- member 0 works in its stream's own set, the others in sets no launch of
                 # EITHER stream uses (a group on the side stream beside split-K layers on the main one: the shortcut groups of the
                 # two encoders.  With `i` alone the ControlNet's conv1 shared slabs and tickets with the UNet encoder's layers: wrong
                 # frames from the captured two-stream form, found by the mini-pipeline parity tests)
                 self._widx = 2 * i + self._sidx
-                descs[i] = self.conv(*a, tile=tile, split_k=own[i] if own else split_k, pipeline=pipeline, _desc_only=True, **kw)
+                descs[i] = self.conv(*a, tile=tile, split_k=own[i] if own else split_k, pipeline=pipeline, inkernel=bool(inkernel),
+                                     _desc_only=True, **CF.unnamed(kw))
         finally:
             self._widx = None
-            self.inkernel_splitk = saved
         self.ctx.call("vsd_conv_gemm_group", descs, len(calls), self.s)
 
-    def group_candidates(self, calls, split=None):
-        """the kernel forms `tune_group` times: GROUP_FORMS at the given split over K (slabs reduced by one more launch for the group,
-        or in the launch), and the members as launches of their own"""
-        stats = any(kw.get("rowstat_out") is not None or kw.get("chanstat_out") is not None or a[3].tile128 for a, kw in calls)
-        if split == self.OWN_SPLIT:  # (entry's split field 0 = every member at its own)
-            own = self.own_splits(calls)
-            if own is None:
-                return [(self.GROUP_ALONE, 1, True, 0)]
-            sp, any_split = 0, max(own) > 1
-        else:
-            sp = split or 1
-            any_split = sp > 1
-        cands = [(t, sp, True, pl) for t, pl in self.GROUP_FORMS]
-        if any_split and not stats:
-            cands += [(t, sp, False, pl) for t, pl in self.GROUP_FORMS]
-        return cands + [(self.GROUP_ALONE, 1, True, 0)]
+    def _stopwatch(self, launch, reps: int, trials: int) -> float:
+        """us per call of `launch`, issued back to back on this stream: two calls to warm up, then the best of `trials` runs of `reps`"""
+        for _ in range(2):
+            launch()
+        best = 1e30
+        for _trial in range(trials):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(self.stream)
+            for _ in range(reps):
+                launch()
+            e1.record(self.stream)
+            e1.synchronize()
+            best = min(best, e0.elapsed_time(e1) / reps * 1e3)
+        return best
+
+    def _time_forms(self, launcher, forms, reps: int, trials: int, what: str):
+        """[(us per call of launcher(form)(), *form)] of every form the library takes, fastest first; none ran: an error that says why"""
+        table, refused = [], None
+        for form in forms:
+            try:
+                table.append((self._stopwatch(launcher(form), reps, trials),) + tuple(form))
+            except RuntimeError as e:
+                refused = e
+        if not table:  # (every form was refused: say for what and why instead of an IndexError)
+            raise RuntimeError(f"{what}: no kernel form ran: {refused}")
+        return sorted(table)
 
     def tune_group(self, calls, reps: int = 12, split=None):
         """time the forms a group may take (`group_candidates`) back to back on this stream; remember the fastest"""
-        table = []
-        for form in self.group_candidates(calls, split):
-            try:
-                for _ in range(2):
-                    self.conv_group(calls, form=form, split=split if split == self.OWN_SPLIT else None)
-                best = 1e30
-                for _trial in range(2):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(self.stream)
-                    for _ in range(reps):
-                        self.conv_group(calls, form=form, split=split if split == self.OWN_SPLIT else None)
-                    e1.record(self.stream)
-                    e1.synchronize()
-                    best = min(best, e0.elapsed_time(e1) / reps * 1e3)
-                table.append((best,) + tuple(form))
-            except RuntimeError:
-                continue
-        if not table:
-            raise RuntimeError("tune_group: no kernel form ran for this group")
-        table.sort()
+        table = self._time_forms(lambda form: partial(self.conv_group, calls, form=form, split=split if split == self.OWN_SPLIT else None),
+                                 self.group_candidates(calls, split), reps, 2, "tune_group")
         b = table[0]
         self.tile_override[self.group_key(calls, split)] = (b[1], b[2], bool(b[3]), b[4])
         return b, table
@@ -540,15 +468,15 @@ class HipOps:
     def pair(self, a, b):
         (fa, aa, ka), (fb, ab, kb) = a, b
         if fa.__name__ == "conv" and fb.__name__ == "conv":
-            sp = self.pair_split(aa, ka, ab, kb)
-            if sp is not None:
+            shared = CF.pair_form(aa, ka, ab, kb, *self._policy(), inkernel=self.inkernel_splitk)
+            if shared is not None:
+                sp, own = shared
                 # Latency mode (one-frame programs): the pair's table entry (`tune_group`, timed alone), else the form its first member
                 # has alone.  Throughput mode (coalesced launches on busy lanes): ALWAYS the members' own form -- a group's entry is
                 # chosen by launch latency, and in such a form a pair of the 5-frame program's layers occupied 14 % more workgroup-time
                 # than the two launches (profiles/round5f_pairs_at_5x4.txt); in their own form the pair costs what they cost and
                 # saves the launch.
-                own_form = self._pair_default if self.tune_mode == 1 else None
-                return self.conv_group([(aa, ka), (ab, kb)], form=own_form, split=sp, default=self._pair_default)
+                return self.conv_group([(aa, ka), (ab, kb)], form=own if self.tune_mode == 1 else None, split=sp, default=own)
             fa(*aa, **ka)
             self._widx = 1
             try:
@@ -571,144 +499,27 @@ class HipOps:
                 self.ctx.check(rc, "vsd_pair_end")
 
     def pair_split(self, aa, ka, ab, kb):
-        """Two twin convs share a grid when both are on the buffer-load operand path (what vsd_conv_gemm_group takes) and the forms
-        they have as launches of their own sum over K in the SAME order -- the same split_k, neither in the halo-patch form (its K
-        order is channel block outer, tap inner).  Then the pair at that split gives the bits the two launches give, and a frame
-        does not depend on which form of the program ran it.  -> that split_k, or None (launch them one by one)."""
-        sp = None
-        for a, k in ((aa, ka), (ab, kb)):
-            g, w = a[2], a[3]
-            if w.cin % 64 or (k.get("c1", 0) or 0) % 64 or (g.hi, g.wi) != (g.hs, g.ws) or g.ksize * g.ksize > 32:
-                return None
-            d = self.conv(*a, _desc_only=True, **k)
-            if d.pipeline == 7 or d.tile in (L.TILE_256x128, L.TILE_256x64, L.TILE_256x256) or (sp is not None and d.split_k != sp):
-                return None
-            if sp is None:
-                self._pair_default = (int(d.tile), int(d.split_k), bool(d.counters) or d.split_k <= 1, int(d.pipeline) if d.pipeline in (5, 8, 9) else 3)
-            sp = int(d.split_k)
-        return sp
-
-    @staticmethod
-    def _halo_call_ok(g, w, c1, act, out_scale, residual2, out2, out_t, rowstat_out, chanstat_out, ln_part) -> bool:
-        """What vsd_conv_gemm's halo-patch form (pipeline 7) accepts: a 3x3 stride-1 conv with the plain epilogue."""
-        plain = all(x is None for x in (residual2, out2, out_t, rowstat_out, chanstat_out, ln_part))
-        return (plain and not w.geglu and g.ksize == 3 and g.stride == 1 and w.cin % 64 == 0 and (c1 or 0) % 64 == 0 and
-                w.n % 8 == 0 and out_scale == 1.0 and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_SILU, L.ACT_RELU | L.ACT_POST))
-
-    @classmethod
-    def _c64_call_ok(cls, g, w, c1, act, out_scale, residual, residual2, out2, out_t, rowstat_out, chanstat_out, ln_part, ldo) -> bool:
-        """What the persistent 64-input-channel form (pipeline 10, csrc/conv_c64.hip) accepts: the halo form's layer with Cin = 64 from one
-        source and Cout = 64 -- or Cout <= 8 into 8-wide rows without a residual (TAESD's 64 -> 3 / 64 -> 4 projections)."""
-        if w.cin != 64 or c1:
-            return False
-        if w.n == 64:
-            return cls._halo_call_ok(g, w, c1, act, out_scale, residual2, out2, out_t, rowstat_out, chanstat_out, ln_part)
-        plain = all(x is None for x in (residual, residual2, out2, out_t, rowstat_out, chanstat_out, ln_part))
-        return (w.n <= 8 and ldo == 8 and plain and not w.geglu and g.ksize == 3 and g.stride == 1 and out_scale == 1.0 and
-                act in (L.ACT_NONE, L.ACT_RELU, L.ACT_SILU))
-
-    # Epilogue classes of the tuning key.  By scripts/wg_timeline.py the epilogue kind moves a workgroup's fixed cost from 1.0
-    # to 4.6 us, and some classes exclude kernel forms (statistics outputs: no reducer kernel; softmax: 128-column tiles;
-    # anything but the plain one: no halo-patch form) -- layers of one (M, N, K) with different epilogues get their own entry.
-    EPI_PLAIN, EPI_LN, EPI_ROWSTAT, EPI_LN_ROWSTAT, EPI_SOFTMAX, EPI_GENERAL, EPI_PLAIN_ACT = range(7)
-
-    @classmethod
-    def epilogue_class(cls, w: PackedConv, rowstat_out=None, ln_part=None, chanstat_out=None, residual2=None, out2=None,
-                       out_scale_dev=None, out_scale=1.0, act=0) -> int:
-        if w.tile128 or (act & 0xff) == L.ACT_SOFTMAX:
-            return cls.EPI_SOFTMAX
-        if chanstat_out is not None or residual2 is not None or out2 is not None or out_scale_dev is not None or out_scale != 1.0:
-            return cls.EPI_GENERAL
-        if ln_part is not None:
-            return cls.EPI_LN_ROWSTAT if rowstat_out is not None else cls.EPI_LN
-        if rowstat_out is not None:
-            return cls.EPI_ROWSTAT
-        # (activations other than none / ReLU / SiLU / ReLU-after-residual leave the halo-patch form: quick-GELU of CLIP)
-        return cls.EPI_PLAIN if (act & 0xff) in (L.ACT_NONE, L.ACT_RELU, L.ACT_SILU, L.ACT_GEGLU) else cls.EPI_PLAIN_ACT
-
-    def conv_key(self, g: Geom, w: PackedConv, t_col0: int = 0, epi: int = 0):
-        # last field: 0 = the choice that is fastest ALONE on an idle GPU (a lone launch: latency), 1 = the choice that costs the
-        # least when FOUR launch lanes are busy (throughput): see tune_conv
-        return (g.m, w.n, w.kp, g.ksize, g.stride, g.hi != g.hs or g.wi != g.ws, w.geglu, t_col0, int(epi), int(self.tune_mode))
+        """the split over K at which two twin convs share a grid, or None: launch them one by one (convform.pair_form)"""
+        shared = CF.pair_form(aa, ka, ab, kb, *self._policy(), inkernel=self.inkernel_splitk)
+        return shared and shared[0]
 
     def conv_key_of(self, g: Geom, w: PackedConv, kwargs: dict):
         """the tuning key of a recorded conv call (args[2], args[3], its keyword arguments)"""
-        return self.conv_key(g, w, kwargs.get("t_col0", 0), self.epilogue_class(
-            w, kwargs.get("rowstat_out"), kwargs.get("ln_part"), kwargs.get("chanstat_out"), kwargs.get("residual2"), kwargs.get("out2"),
-            kwargs.get("out_scale_dev"), kwargs.get("out_scale", 1.0), kwargs.get("act", L.ACT_NONE)))
+        return CF.conv_call(g, w, **kwargs).key(self.tune_mode)
 
     def tune_conv(self, args, kwargs, reps: int = 12):
         """Time every (tile, split_k, reduction form) candidate for one recorded conv call on the GPU and
         remember the fastest in tile_override.  Returns (best, table)."""
         g, w = args[2], args[3]
-        t_col0 = kwargs.get("t_col0", 0)
-        key = self.conv_key_of(g, w, kwargs)
-        kt = w.kp // 64
-        wide = w.geglu or w.tile128  # epilogues that need whole 128-column tiles and no split-K
-        tiles = [L.TILE_128x128, L.TILE_64x128] if wide else [L.TILE_128x128, L.TILE_128x64, L.TILE_64x128, L.TILE_64x64]
-        # the 256x128 tile (buffer-load path only: Cin % 64 == 0, no resize) pays when M is large (batched frames, TAESD)
-        big_path = w.cin % 64 == 0 and (kwargs.get("c1", 0) or 0) % 64 == 0 and (g.hi, g.wi) == (g.hs, g.ws)
-        big_ok = big_path and g.m >= 1024
-        if big_ok:
-            tiles = tiles + [L.TILE_256x128]
-        # the 256x256 tile (eight waves, unsplit, row-banded epilogue): least L2 -> LDS fill per FLOP; for layers with enough of both
-        # M and N to give the chip's lanes something to do (a softmax / transposed-output tile is 128 columns: not for those)
-        huge_ok = (big_path and g.m >= 1024 and w.n >= 512 and not w.tile128 and kwargs.get("out_t") is None and
-                   kwargs.get("chanstat_out") is None and not self.no_w8 and self.tune_mode == 1)
-        # (both only among the throughput-mode candidates: alone on an idle chip the eight-wave forms measure 0-40 % slower than
-        #  the four-wave ones, with four lanes busy 7-18 % faster on the wide 1 x 1 layers -- profiles/round6_w8_probe_*.txt)
+        call = CF.conv_call(g, w, **kwargs)
+        key = call.key(self.tune_mode)
+        cands = CF.candidates(call, self.tune_mode, CF.flags_of(self))
+        kw = CF.unnamed(kwargs)
+        self.tile_override.pop(key, None)
 
-        plain_epi = all(kwargs.get(k) is None for k in ("out2", "residual2", "out_t", "rowstat_out", "chanstat_out", "ln_part"))
-        act = kwargs.get("act", L.ACT_NONE)
-        halo_ok = (not wide and g.ksize == 3 and g.stride == 1 and w.cin % 64 == 0 and
-                   (kwargs.get("c1", 0) or 0) % 64 == 0 and w.n % 8 == 0 and plain_epi and
-                   kwargs.get("out_scale", 1.0) == 1.0 and act in (L.ACT_NONE, L.ACT_RELU, L.ACT_SILU, L.ACT_RELU | L.ACT_POST))
-        cands = [(L.TILE_256x256, 1, False, pl) for pl in (8, 9)] if huge_ok else []
-        for t in tiles:
-            bm, bn = L.TILE_DIMS[t]
-            if kwargs.get("out_t") is not None and t_col0 % bn:
-                continue
-            blocks = -(-g.m // bm) * -(-w.n // bn)
-            # pipelines 8 / 9: the 3-stage ring on eight waves (two per SIMD), buffer-load path, tiles of 128 x 128 and larger
-            w8 = (8, 9) if big_path and bm * bn >= 128 * 128 and not self.no_w8 and self.tune_mode == 1 else ()
-            for pl in ((3, 5) if t == L.TILE_256x128 else (0, 3, 4, 5, 6)) + w8:
-                cands.append((t, 1, False, pl))
-            if halo_ok and bm == 128:  # LDS halo patch (pipeline 7); split-K (over channel blocks) = the two-kernel form
-                hblocks = g.batch * -(-g.ho // 8) * -(-g.wo // 16) * -(-w.n // bn)
-                for sp in (1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20):
-                    if sp > w.cin // 64 or (sp > 1 and hblocks * sp > 1536):
-                        break
-                    cands.append((t, sp, False, 7))
-                    if sp > 1 and hblocks <= L.SPLITK_MAX_TILES:
-                        cands.append((t, sp, True, 7))
-            if w.geglu or blocks >= 384:
-                continue
-            for sp in (2, 3, 4, 6, 8, 12, 16, 24):
-                if sp > kt // 2 or blocks * sp > 1536:
-                    break
-                for pl in ((3, 5) if t == L.TILE_256x128 else (0, 3, 5)) + w8:
-                    if kwargs.get("rowstat_out") is None and kwargs.get("chanstat_out") is None and not w.tile128:
-                        cands.append((t, sp, False, pl))
-                    cands.append((t, sp, True, pl))
-        if halo_ok:  # 16x16 patches (8 waves): half the weight traffic of the 8x16 patch
-            for t in (L.TILE_256x128, L.TILE_256x64):
-                bn = L.TILE_DIMS[t][1]
-                hblocks = g.batch * -(-g.ho // 16) * -(-g.wo // 16) * -(-w.n // bn)
-                for sp in (1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20):
-                    if sp > w.cin // 64 or (sp > 1 and hblocks * sp > 1536):
-                        break
-                    cands.append((t, sp, False, 7))
-                    if sp > 1 and hblocks <= L.SPLITK_MAX_TILES:
-                        cands.append((t, sp, True, 7))
-        # the persistent 64 -> 64 channel form (csrc/conv_c64.hip, pipeline 10): TAESD's block convs
-        if not self.no_c64 and not wide and kwargs.get("out_scale_dev") is None and self._c64_call_ok(
-                g, w, kwargs.get("c1", 0) or 0, act, kwargs.get("out_scale", 1.0), kwargs.get("residual"), kwargs.get("residual2"), kwargs.get("out2"),
-                kwargs.get("out_t"), kwargs.get("rowstat_out"), kwargs.get("chanstat_out"), kwargs.get("ln_part"),
-                kwargs.get("ldo") if kwargs.get("ldo") is not None else w.n_out):
-            cands.append((L.TILE_256x64, 1, False, 10))
-        kw = {k: v for k, v in kwargs.items() if k not in ("tile", "split_k", "pipeline")}
-        table = []
-        saved = self.tile_override.pop(key, None)
+        # every candidate alone, back to back (in throughput mode once: a pre-pass; else twice, the better run counts)
+        table = self._time_forms(lambda form: partial(self.conv, *args, **form._asdict(), **kw), cands, reps, 1 if self.tune_mode == 1 else 2,
+                                 f"tune_conv M={g.m} N={w.n} K={w.k} ksize={g.ksize}")
         if self.tune_mode == 1:
             # Throughput mode.  Timed alone, a candidate is judged by its launch latency on an idle chip -- small tiles and many
             # workgroups win.  With four lanes busy the chip is shared, other launches fill whatever a launch leaves idle, and
@@ -716,43 +527,13 @@ class HipOps:
             # MI355X (scripts/tune_lanes_probe.py, us per launch alone | with four copies in flight): 5x32x32 640->640 3x3:
             # 64x128 GEMM form 54.8 | 48.9, 256x128 halo form 81.6 | 38.7; 1280x1280x5120: 64x64 35.2 | 30.4, 128x64 42.3 | 23.8.
             # So: every candidate alone first (cheap), then the ones within 2.5x of the best with four copies at once.
-            alone = self._time_candidates(args, kw, cands, reps)
-            if not alone:
-                raise RuntimeError("tune_conv: no candidate ran")
-            cut = 2.5 * alone[0][0]
+            cut = 2.5 * table[0][0]
             # (the 256 x 256 tile always makes the shortlist: a handful of workgroups is slow ALONE by construction -- 2-5 x on an idle
             #  chip -- and what it is for is the shared one)
-            short = [(t, sp, ink, pl) for (us, t, sp, ink, pl) in alone if us <= cut or (t == L.TILE_256x256 and us <= 6.0 * alone[0][0])]
-            table = self._time_candidates_on_lanes(args, kw, short, reps) or alone
-            self.inkernel_splitk = True
-            best = table[0]
-            self.tile_override[key] = (best[1], best[2], best[3], best[4])
-            return best, table
-        last_error = None
-        for (t, sp, ink, pl) in cands:
-            self.inkernel_splitk = ink
-            try:
-                for _ in range(2):
-                    self.conv(*args, tile=t, split_k=sp, pipeline=pl, **kw)
-                best_us = 1e30
-                for _trial in range(2):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(self.stream)
-                    for _ in range(reps):
-                        self.conv(*args, tile=t, split_k=sp, pipeline=pl, **kw)
-                    e1.record(self.stream)
-                    e1.synchronize()
-                    best_us = min(best_us, e0.elapsed_time(e1) / reps * 1e3)
-                table.append((best_us, t, sp, ink, pl))
-            except RuntimeError as e:
-                last_error = e
-                continue
-        self.inkernel_splitk = True
-        if not table:  # (every candidate was refused: say for which layer and why instead of an IndexError)
-            raise RuntimeError(f"tune_conv: no candidate ran for M={g.m} N={w.n} K={w.k} ksize={g.ksize}: {last_error}")
-        table.sort()
+            short = [CF.Form(*row[1:]) for row in table if row[0] <= cut or (row[1] == L.TILE_256x256 and row[0] <= 6.0 * table[0][0])]
+            table = self._time_candidates_on_lanes(args, kw, short, reps) or table
         best = table[0]
-        if best[2] > 1 and not best[3] and self.one_launch_bias_us > 0:
+        if self.tune_mode != 1 and best[2] > 1 and not best[3] and self.one_launch_bias_us > 0:
             # a two-launch form won: take a one-launch form that is within the bias instead (one graph node less; back-to-back
             # timing on an otherwise idle GPU flatters the second launch, which in a frame also delays the NEXT layer's start)
             for cand in table[1:]:
@@ -763,27 +544,6 @@ class HipOps:
                     break
         self.tile_override[key] = (best[1], best[2], best[3], best[4])
         return best, table
-
-    def _time_candidates(self, args, kw, cands, reps):
-        """us per launch of every candidate, alone, back to back on this object's stream; sorted"""
-        table = []
-        for (t, sp, ink, pl) in cands:
-            self.inkernel_splitk = ink
-            try:
-                for _ in range(2):
-                    self.conv(*args, tile=t, split_k=sp, pipeline=pl, **kw)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(self.stream)
-                for _ in range(reps):
-                    self.conv(*args, tile=t, split_k=sp, pipeline=pl, **kw)
-                e1.record(self.stream)
-                e1.synchronize()
-                table.append((e0.elapsed_time(e1) / reps * 1e3, t, sp, ink, pl))
-            except RuntimeError:
-                continue
-        self.inkernel_splitk = True
-        table.sort()
-        return table
 
     def _time_candidates_on_lanes(self, args, kw, cands, reps, n_lanes: int = 4):
         """us per launch with `n_lanes` copies of the candidate in flight, one per launch lane (captured graphs of `reps`
@@ -809,17 +569,16 @@ class HipOps:
                     kwl[name] = kwl[name].clone()
             per_lane.append((src0.clone(), None if src1 is None else src1.clone(), out.clone(), kwl))
         table = []
-        for (t, sp, ink, pl) in cands:
+        for form in cands:
             graphs = []
             try:
                 for o, (a0, a1, oo, kwl) in zip(lanes, per_lane):
-                    o.inkernel_splitk = ink
-                    o.conv(a0, a1, g, w, oo, *args[5:], tile=t, split_k=sp, pipeline=pl, **kwl)
+                    o.conv(a0, a1, g, w, oo, *args[5:], **form._asdict(), **kwl)
                     o.synchronize()
                     o.graph_begin()
                     try:
                         for _ in range(reps):
-                            o.conv(a0, a1, g, w, oo, *args[5:], tile=t, split_k=sp, pipeline=pl, **kwl)
+                            o.conv(a0, a1, g, w, oo, *args[5:], **form._asdict(), **kwl)
                     finally:
                         graphs.append((o, o.graph_end()))
                 best = 1e30
@@ -833,46 +592,38 @@ class HipOps:
                     for o, gr in graphs:
                         o.synchronize()
                     best = min(best, (time.perf_counter() - t0) / (2 * reps * len(graphs)) * 1e6)
-                table.append((best, t, sp, ink, pl))
+                table.append((best,) + form)
             except RuntimeError:
                 pass
             finally:
                 for o, gr in graphs:
                     o.graph_destroy(gr)
-                for o in lanes:
-                    o.inkernel_splitk = True
         table.sort()
         return table
 
     # ---- tuning table persistence (the "find" results are per device generation and shape)
+    @staticmethod
+    def _read_table(path: str):
+        """[(key, entry)] of the table file at `path`; none when there is no such file"""
+        if not _os.path.exists(path):
+            return []
+        return [(tuple(k), tuple(v)) for k, v in json.load(open(path)).get("table", [])]
+
     def save_tuning(self, path: str):
         """Write this process's choices INTO the table at `path` (entries of other shapes -- other batch sizes, other
         frame sizes -- are kept)."""
-        import json
-        import os
-
-        merged = {}
-        if os.path.exists(path):
-            try:
-                for k, v in json.load(open(path)).get("table", []):
-                    merged[tuple(bool(x) if isinstance(x, bool) else x for x in k)] = tuple(v)
-            except Exception:
-                merged = {}
+        try:
+            merged = dict(self._read_table(path))
+        except Exception:
+            merged = {}
         merged.update(self.tile_override)
         with open(path, "w") as f:
             json.dump({"device": torch.cuda.get_device_name(self.device),
                        "table": [[list(k), list(v)] for k, v in sorted(merged.items(), key=str)]}, f, indent=0)
 
     def load_tuning(self, path: str) -> int:
-        import json
-        import os
-
-        if not os.path.exists(path):
-            return 0
-        d = json.load(open(path))
         n = 0
-        for k, v in d.get("table", []):
-            key = tuple(bool(x) if isinstance(x, bool) else x for x in k)
+        for key, v in self._read_table(path):
             if isinstance(key[-1], bool):
                 continue  # a round-3 table (last field: "has a statistics output"): its entries name no epilogue class
             if len(key) == 9 and key[0] != "group":

@@ -4,6 +4,7 @@ from typing import List, Tuple
 
 import torch
 
+from . import convform as CF
 from .packing import _round_up as _ru
 
 
@@ -113,14 +114,10 @@ def launches_by_kind(ops, program: Recorder):
         fused = ((hw <= 256 and cpg <= 40) or (hw <= 1024 and cpg <= 20)) and cpg in (40, 8, 16, 20, 4, 12, 10, 2, 6)
         return 1 if fused else 2
 
-    def table(key):
-        ent = ops.tile_override.get(key)
-        if ent is None and key[-1] == 1:
-            ent = ops.tile_override.get(key[:-1] + (0,))
-        return ent
+    table, mode, flags = ops.tile_override, getattr(ops, "tune_mode", 0), CF.flags_of(ops)
 
     def conv_reducer(a, k):
-        ent = table(ops.conv_key_of(a[2], a[3], k))
+        ent = CF.lookup(table, CF.recorded(a, k).key(mode))
         return int(ent is not None and ent[1] > 1 and not ent[2] and not a[3].tile128)
 
     for fn, a, k in program.calls:
@@ -131,13 +128,14 @@ def launches_by_kind(ops, program: Recorder):
             (fa, aa, ka), (fb, ab, kb) = a
             op = fa.__name__
             if op == "conv":
-                sp = ops.pair_split(aa, ka, ab, kb)
-                ent = table(ops.group_key([(aa, ka), (ab, kb)], sp)) if sp is not None else (ops.GROUP_ALONE,)
-                if sp is not None and getattr(ops, "tune_mode", 0) == 1:  # (throughput mode: the members' own form, ops.pair)
-                    ent = ops._pair_default
-                if ent is None:
-                    ent = (0, sp, True, 3)
-                if ent[0] != ops.GROUP_ALONE:
+                shared = CF.pair_form(aa, ka, ab, kb, table, mode, flags, inkernel=getattr(ops, "inkernel_splitk", True))
+                ent = CF.ALONE
+                if shared is not None:
+                    # throughput mode: the members' own form, as ops.pair.  A pair without an entry counts as reduced in the launch, as
+                    # it always has here, although ops.pair runs it in the first member's own form (docs/NOTEBOOK.md: to follow up)
+                    sp, own = shared
+                    ent = own if mode == 1 else CF.lookup(table, CF.group_key([(aa, ka), (ab, kb)], sp, mode)) or CF.Form(0, sp, True, 3)
+                if ent[0] != CF.GROUP_ALONE:
                     count("pair_conv")
                     count("pair_splitk_reduce", int(ent[1] > 1 and not ent[2]))
                 else:
@@ -154,9 +152,9 @@ def launches_by_kind(ops, program: Recorder):
             continue
         if name == "conv_group":
             split = k.get("split")
-            own = ops.own_splits(a[0]) if split == getattr(ops, "OWN_SPLIT", None) and hasattr(ops, "own_splits") else None
-            ent = table(ops.group_key(a[0], split)) if hasattr(ops, "group_key") else None
-            if (split is not None and own is None) or (ent is not None and ent[0] == ops.GROUP_ALONE):
+            own = CF.own_splits(a[0], table, mode, flags) if split == CF.OWN_SPLIT else None
+            ent = CF.lookup(table, CF.group_key(a[0], split, mode))
+            if (split is not None and own is None) or (ent is not None and ent[0] == CF.GROUP_ALONE):
                 for aa, kk in a[0]:  # (a group whose table entry -- or a member's own form -- sends the members out alone)
                     count("conv")
                     count("splitk_reduce", conv_reducer(aa, kk))
