@@ -5,6 +5,7 @@ server.py:104-143), one worker process per GPU, frames sharded round-robin, drop
 
   python examples/frame_loop.py --gpus 1 --fps 60 --seconds 10 --batch 3          (needs the MI355X)
   python examples/frame_loop.py --factory helpers_fake_pipeline:FakePipeline ...   (any stand-in with the same surface)
+  python examples/frame_loop.py --fade-to "a charcoal sketch" --fade-frames 60 ...  (a cross-fade between two prompts, written as 60 mixes)
 
 Prints one JSON line: frames offered / processed / dropped, output frames per second, p50 / p95 submit->result latency.
 """
@@ -29,6 +30,15 @@ def camera_frame(k: int, w: int, h: int) -> Image.Image:
     yy, xx = np.mgrid[0:h, 0:w]
     a = rng.integers(0, 256, (h, w, 3), dtype=np.uint8) // 2 + ((xx * 2 + yy + 17 * k) % 256).astype(np.uint8)[..., None] // 2
     return Image.fromarray(a.astype(np.uint8), "RGB")
+
+
+def crossfade(a: str, b: str, k: int, frames: int):
+    """The prompt of frame k of a cross-fade from text `a` to text `b` over `frames` frames: a MIX of the two (`{"mix": [[a, 1 - t], [b, t]]}`,
+    what `infer` takes besides a text).  The workers blend the two cached prompts on the device, one small launch per new value; nothing is
+    encoded or built after the two texts are cached.  `infer` cannot tell sessions apart, so a fade is the caller's: k mixes, written out."""
+    if frames <= 0 or k >= frames:
+        return b
+    return {"mix": [[a, 1.0 - k / frames], [b, k / frames]]}  # (k = 0 comes down to the plain prompt `a`)
 
 
 async def run(args):
@@ -60,7 +70,10 @@ async def run(args):
         while time.perf_counter() - t0 < args.seconds:
             frame = pool[k % len(pool)]
             now = time.perf_counter()
-            ticket = disp.submit(frame, **opts)
+            if args.fade_to:  # frame k of the stream carries value k of the fade
+                ticket = disp.submit(frame, **dict(opts, prompt=crossfade(args.prompt, args.fade_to, k, args.fade_frames)))
+            else:
+                ticket = disp.submit(frame, **opts)
             if ticket is not None:
                 t_sub[ticket] = now
             k += 1
@@ -93,6 +106,8 @@ def main(argv=None):
     ap.add_argument("--model", default="SimianLuo/LCM_Dreamshaper_v7")
     ap.add_argument("--controlnet", default="lllyasviel/control_v11p_sd15_canny")
     ap.add_argument("--prompt", default="pixar, cg")
+    ap.add_argument("--fade-to", dest="fade_to", default="", help="cross-fade from --prompt to this prompt, as prompt mixes")
+    ap.add_argument("--fade-frames", dest="fade_frames", type=int, default=60, help="frames the cross-fade takes")
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--strength", type=float, default=0.6)

@@ -312,6 +312,49 @@ typedef struct vsd_prompt_seg {
 } vsd_prompt_seg;
 int vsd_prompt_install(vsd_ctx* ctx, const void* src_block, void* dst_block, const vsd_prompt_seg* segs_dev, int nseg, int frame, void* stream);
 
+/* ---- THE PROMPT MIX: a weighted mix of cached prompts, formed on the device (csrc/prompt_mix.hip, csrc/prompt_mix_core.h) -------------
+ * Every item of a prompt's constants that depends on the prompt is LINEAR in the text embeddings: K and V^T are to_k / to_v of them
+ * (no bias); the absorbed query weights G = scale * K_h * Wq_h and their LayerNorm fold ln_s / ln_t are linear in K; the absorbed output
+ * weights Z = Wo_h * V_h^T are linear in V.  So the constants of the embeddings sum(w_i * e_i) are, up to fp16 rounding,
+ * sum(w_i * constants(e_i)), and a blend of prompts that are already cached needs no build: one memory-bound pass.
+ * A MIX is 1 to VSD_MIX_MAX components (block, weight).  The weights are fp32, finite and >= 0; the HOST makes them sum to 1: each is
+ *   fp32(w_i / sum(w)) with the quotient taken in fp64 (videosd_amd/promptmix.py, which also states the canonical form of a mix: repeated
+ *   texts merged, zero weights dropped, components ordered by text, a mix of one component IS that prompt).
+ * ELEMENT ARITHMETIC.  fp16 element (VSD_MIX_F16): acc = w_0 * x_0, an fp32 multiply of the fp32 weight and the element widened to fp32;
+ *   then acc = fma(w_i, x_i, acc), one fp32 fma, for i = 1 .. n-1 in component order; the output is fp16(acc), one rounding to nearest
+ *   even.  fp32 element (VSD_MIX_F32; the LayerNorm fold): the same chain, the output is acc.  Nothing is contracted or reassociated.
+ * Items that do NOT depend on the prompt (VSD_MIX_COPY; today the absorbed output bias, to_out.0.bias) are copied from component 0, never
+ *   summed: fp32 weights that sum to 1 only approximately must not move a bias.
+ * ONE component has weight exactly 1.0f after normalisation; its bytes are written unchanged, whatever the kind and whatever they hold.
+ *   Zero padding (V^T columns beyond tl, the unused rows of the absorbed weights) stays zero: weights >= 0 give +0 from +0.
+ *   With n >= 2 the bit pattern of a NaN result is not specified (a cached prompt holds none).
+ * ADDRESSING is vsd_prompt_install's, with the element kind added: segment i takes `rows` rows of `row_bytes` bytes, dense from byte
+ *   src_off on in EVERY source block (the components share one layout), to dst_off + frame * dst_frame_stride + row * dst_pitch.  The
+ *   destination is either a whole block of the sources' layout (every item one run: rows = 1, dst_off = src_off, dst_pitch =
+ *   dst_frame_stride = row_bytes, frame = 0) or one frame slot of a per-frame block (the K / V^T segments of vsd_prompt_install).  Every
+ *   field but `rows` and `kind` is in bytes and a multiple of 16; rows >= 1; dst_pitch is the same whole number B of dst_frame_stride in
+ *   every segment, dst_frame_stride >= row_bytes; reserved = 0.
+ * vsd_prompt_mix: ONE launch on `stream` for all segments.  src_blocks (n device pointers) and weights (n floats) are HOST arrays and
+ *   travel as launch arguments: nothing is uploaded, nothing allocated, nothing waits.  The sources must stay allocated and unchanged
+ *   until the launch has executed; dst_block must not overlap them.  segs_dev: the table in DEVICE memory, 16-byte aligned.
+ * vsd_prompt_mix_table: checks a table and remembers it by address (one blocking copy; the engine's prepare) so that no later call waits;
+ *   vsd_prompt_mix does the same for a table it has not seen.  A table must not change afterwards; nseg = 0 forgets it.
+ * vsd_prompt_mix_host: the same arithmetic and addressing as plain host loops on host memory (segs: a HOST array); no GPU, no context.
+ * VSD_ERR_ARG with a reason, before anything is launched or written: n outside 1..VSD_MIX_MAX; a null or misaligned (16 bytes) block or
+ *   table; a weight that is negative or not finite; a field that is no multiple of 16, an unknown kind; frame outside [0, B); nseg outside
+ *   1..65535.  The blocks' SIZES are the caller's: src_off + rows * row_bytes must lie inside every source, the largest
+ *   dst_off + (rows - 1) * dst_pitch + B * dst_frame_stride inside dst_block. */
+#define VSD_MIX_MAX 4
+enum { VSD_MIX_F16 = 0, VSD_MIX_F32 = 1, VSD_MIX_COPY = 2 };
+typedef struct vsd_mix_seg {
+  int64_t src_off, dst_off, rows, row_bytes, dst_pitch, dst_frame_stride, kind, reserved;
+} vsd_mix_seg;
+int vsd_prompt_mix_table(vsd_ctx* ctx, const vsd_mix_seg* segs_dev, int nseg);
+int vsd_prompt_mix(vsd_ctx* ctx, const void* const* src_blocks, const float* weights, int n, void* dst_block, const vsd_mix_seg* segs_dev,
+                   int nseg, int frame, void* stream);
+int vsd_prompt_mix_host(const void* const* src_blocks, const float* weights, int n, void* dst_block, const vsd_mix_seg* segs, int nseg,
+                        int frame);
+
 /* ---- per-frame options: strength and ControlNet scale per frame of one launch (csrc/noise.hip, csrc/norm.hip, csrc/frame_options.hip) ----
  * `strength` decides the timesteps (scheduler coefficients, time embeddings) and `controlnet_scale` the 13 residual scales.  The default
  * program reads one set of each per PLAN; a program recorded with Engine.prepare(frame_options=True) reads them per FRAME of the launch

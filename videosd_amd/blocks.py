@@ -6,6 +6,7 @@ from typing import Dict, List
 import torch
 
 from .lcm import LCMSchedule
+from .lib import MIX_COPY, MIX_F16, MIX_F32, MIX_MAX
 from .packing import PackedConv
 from .packing import _round_up as _ru
 
@@ -85,6 +86,34 @@ def prompt_segments(src: PromptLayout, dst: FramePromptLayout):
             c, ldt = sshape
             segs.append((soff, doff, c, ldt * 2, B * ldt * 2, ldt * 2))
     assert all(v % 16 == 0 for sg in segs for v in sg[:2] + sg[3:])
+    return segs
+
+
+# How every item NAME of a PromptLayout takes part in a prompt mix (include/vsd.h THE PROMPT MIX).  Linear in the text embeddings: K and V^T
+# are to_k / to_v of them, xa1_w / xa1_s / xa1_t are G = scale * K_h * Wq_h and its LayerNorm fold, xa2_w is Z = Wo_h * V_h^T.  xa2_b is
+# to_out.0.bias: it does not depend on the prompt and is copied, never summed.  A new item name has no entry here and `mix_segments` refuses
+# it until someone decides which kind it is (tests/test_prompt_mix_host.py proves the linear ones linear).
+MIX_ITEM_KINDS = {"k": MIX_F16, "vt": MIX_F16, "xa1_w": MIX_F16, "xa1_s": MIX_F32, "xa1_t": MIX_F32, "xa2_w": MIX_F16, "xa2_b": MIX_COPY}
+
+
+def mix_segments(src: PromptLayout, dst):
+    """The segment list of `vsd_prompt_mix` (include/vsd.h vsd_mix_seg) that writes a mix of prompts of layout `src` into a block of layout
+    `dst`: per tensor (src_off, dst_off, rows, row_bytes, dst_pitch, dst_frame_stride, kind, 0).  `dst is src`: a whole block, every item one
+    run in place.  `dst` a FramePromptLayout: ONE frame slot, the K / V^T segments of `prompt_segments` as fp16 mixes."""
+    if dst is src:
+        segs = []
+        for (_ni, _bi, name), (off, shape, dtype) in src.items.items():
+            if name not in MIX_ITEM_KINDS:
+                raise ValueError(f"prompt mix: the item {name!r} of a prompt's constants has no entry in blocks.MIX_ITEM_KINDS: is it linear in "
+                                 "the text embeddings, or independent of the prompt?")
+            n = torch.empty(0, dtype=dtype).element_size()
+            for d in shape:
+                n *= d
+            n = _ru(n, 16)  # (items start at multiples of 256: the bytes up to the next chunk are the block's own padding)
+            segs.append((off, off, 1, n, n, n, MIX_ITEM_KINDS[name], 0))
+    else:
+        segs = [sg + (MIX_ITEM_KINDS[key[2]], 0) for sg, key in zip(prompt_segments(src, dst), dst.items)]
+    assert all(v % 16 == 0 for sg in segs for v in sg[:2] + sg[3:6])
     return segs
 
 
@@ -185,19 +214,51 @@ class PromptBlock:
         return got
 
 
+class PromptMix:
+    """A weighted mix of cached prompts (include/vsd.h THE PROMPT MIX): 1..4 PromptBlocks of ONE layout and their fp32 weights (made to sum
+    to 1 by promptmix.normalized).  It has no bytes of its own: an engine forms it in its own block, or in a frame slot, by one
+    `prompt_mix` launch.  It holds references to its components, so a component evicted from a prompt cache lives as long as something
+    that reads it."""
+
+    def __init__(self, components, weights):
+        self.components, self.weights = tuple(components), tuple(float(w) for w in weights)
+        if not 1 <= len(self.components) <= MIX_MAX or len(self.weights) != len(self.components):
+            raise ValueError(f"a prompt mix has 1..{MIX_MAX} components and one weight each, got {len(self.components)} component(s) and "
+                             f"{len(self.weights)} weight(s)")
+        if any(not (w >= 0.0 and w != float("inf")) for w in self.weights):
+            raise ValueError(f"the weights of a prompt mix are finite and not negative, got {list(self.weights)}")
+        self.layout = self.components[0].layout
+        if any(c.layout is not self.layout for c in self.components):
+            raise ValueError(f"all components of a prompt mix must have the same text length, got {[c.layout.tl for c in self.components]}")
+
+    def same_as(self, other) -> bool:
+        """the same component blocks with the same weights: what is installed need not be formed again"""
+        return (isinstance(other, PromptMix) and len(other.components) == len(self.components) and
+                all(a is b for a, b in zip(self.components, other.components)) and self.weights == other.weights)
+
+
+def same_source(a, b) -> bool:
+    """do the sources `a` and `b` of a prompt install give the same bytes without looking at them? (the same object, or equal mixes)"""
+    return a is b or (isinstance(a, PromptMix) and a.same_as(b))
+
+
 class FrameSlots:
     """The frame slots of a device block (`buf`, laid out by `layout`, one slot per frame of a launch): which source each slot holds (a
-    reference: the source outlives its install), and `prompt_install` for every slot whose source changed.  A source is anything with
-    `.buf` and `.layout` (a PromptBlock, an OptionEntry)."""
+    reference: the source outlives its install), and `prompt_install` -- `prompt_mix` for a PromptMix -- for every slot whose source
+    changed.  A source is anything with `.buf` and `.layout` (a PromptBlock, an OptionEntry), or a PromptMix of such."""
 
     def __init__(self, buf, layout):
         self.buf, self.layout = buf, layout
         self.src = [None] * layout.frames
 
     def install(self, ops, want, seg_table):
-        """want: one source per slot; seg_table(source layout, this layout) -> (device table, segments)"""
+        """want: one source per slot; seg_table(source layout, this layout[, mix=True]) -> (device table, segments)"""
         for f, s in enumerate(want):
-            if s is not self.src[f]:
-                tab, nseg = seg_table(s.layout, self.layout)
-                ops.prompt_install(s.buf, self.buf, tab, nseg, f)
+            if not same_source(s, self.src[f]):
+                if isinstance(s, PromptMix):
+                    tab, nseg = seg_table(s.layout, self.layout, mix=True)
+                    ops.prompt_mix([c.buf for c in s.components], s.weights, self.buf, tab, nseg, f)
+                else:
+                    tab, nseg = seg_table(s.layout, self.layout)
+                    ops.prompt_install(s.buf, self.buf, tab, nseg, f)
                 self.src[f] = s

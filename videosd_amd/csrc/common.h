@@ -58,6 +58,7 @@ struct vsd_ctx {
   double fam_flops[VSD_FAM_COUNT];
   int64_t fam_launch[VSD_FAM_COUNT];
   std::unordered_map<const void*, std::pair<int, int>> prompt_tables;  // vsd_prompt_install: table -> (segments, frame slots), once checked
+  std::unordered_map<const void*, std::pair<int, int>> mix_tables;     // vsd_prompt_mix: table -> (segments, frame slots), once checked
   std::unordered_map<const void*, std::pair<int, int>> merge_tables;   // vsd_cn_merge_frames: table -> (segments, largest scale column), once checked
 };
 

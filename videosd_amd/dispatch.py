@@ -42,6 +42,7 @@ from typing import Any, Dict, List, Optional
 
 import torch
 
+from . import promptmix as PM
 from .frames import I420Frame, av_plane_views, is_i420
 from .transport import _ShmRing, decode_frame, encode_frame, is_frame, is_slot_ref
 
@@ -156,8 +157,8 @@ def _wait_with_deadline(work, timeout: float, poll_s: float = 0.0005):
 
 
 def prompt_key(prompt):
-    """The cache key VideoSDPipeline uses for a prompt (str, or list[str] as in the reference's default)."""
-    return prompt if isinstance(prompt, str) else tuple(prompt)
+    """The cache key VideoSDPipeline uses for a prompt (str, list[str] as in the reference's default, or a mix: promptmix.prompt_key)."""
+    return PM.prompt_key(prompt)
 
 
 def free_port() -> int:
@@ -1106,7 +1107,17 @@ class FrameDispatcher:
         return self.healthy[g] and not getattr(p, "dead", False) and (proc is None or proc.is_alive())
 
     def _sync_prompt(self, options):
-        prompt = options.get("prompt", INFER_DEFAULTS["prompt"])
+        """Ahead of a frame: every worker gets the prompt(s) the frame needs that it is not known to hold.  A MIX (promptmix.py) needs its
+        component texts and nothing else: one sync per component that is neither known nor on its way, never one for the mix -- each rank
+        forms the mix from its own cached components by the same arithmetic, so every rank produces the same bits."""
+        try:
+            parts = PM.component_prompts(options.get("prompt", INFER_DEFAULTS["prompt"]))
+        except ValueError:
+            return  # (not a mix after all: the worker refuses the frame and says why)
+        for prompt in parts:
+            self._sync_one_prompt(prompt, options)
+
+    def _sync_one_prompt(self, prompt, options):
         key = prompt_key(prompt)
         if not self.group_ok and not self._had_group:
             return  # stand-alone handles: each worker encodes a prompt when its first frame with it arrives

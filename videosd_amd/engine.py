@@ -26,7 +26,8 @@ import torch
 
 from . import lib as L
 from .blocks import (FRAME_OPTION_OPS, MAX_OPTION_ENTRIES, FramePromptLayout, FrameSlots, OptionEntry, OptionLayout,  # noqa: F401
-                     PromptBlock, PromptLayout, controlnet_scales, option_segments, prompt_segments, schedule_constants)
+                     PromptBlock, PromptLayout, PromptMix, controlnet_scales, mix_segments, option_segments, prompt_segments, same_source,
+                     schedule_constants)
 from .config import ControlNetConfig, TAESDConfig, UNetConfig
 from .convform import OWN_SPLIT, lookup
 from .lcm import LCMSchedule, timestep_sinusoid, w_embedding
@@ -154,7 +155,7 @@ class Engine:
         self._reset_plan_state()
         # the prompt: outlives a plan (a `prepare` for the same text length keeps the block and what it holds)
         self.pblock = None          # this engine's own prompt constants (the addresses its program / graph reads)
-        self._installed = None      # the PromptBlock whose bytes a single-prompt `pblock` currently holds
+        self._installed = None      # the PromptBlock (or PromptMix) whose bytes a single-prompt `pblock` currently holds
         self._want = None           # `use_prompt`: this engine's prompt (None: the family default)
         self._want_list = None      # `use_prompts`: one PromptBlock per frame of the launch (None: `_want` / the default for every frame)
         self._prompt_slots = None   # FrameSlots of a per-frame `pblock` (`prepare(frame_prompts=True)`): the PromptBlock each slot holds
@@ -274,7 +275,9 @@ class Engine:
     def use_prompt(self, blk: Optional[PromptBlock]):
         """This engine's launches use `blk` (from `build_prompt`, e.g. a prompt cache entry) from the next launch on, whatever
         the other engines of the family run; None: follow the family default again.  Call it with no launch of THIS engine
-        in flight (the other lanes are not affected: every engine reads its own copy)."""
+        in flight (the other lanes are not affected: every engine reads its own copy).
+        `blk` may be a PromptMix of such blocks (include/vsd.h THE PROMPT MIX): the engine then forms the mix in its own block by ONE
+        `prompt_mix` launch where a block takes one copy -- stream-ordered, no allocation, nobody waits; the same mix again costs nothing."""
         self._want = blk
         self._want_list = None
 
@@ -282,7 +285,8 @@ class Engine:
         """`frame_prompts` engines: frame i of this engine's launches uses blks[i] (one `build_prompt` result per frame of the launch, e.g.
         prompt cache entries; the same object may appear several times) from the next launch on.  Only the frame slots whose entry
         changed since this engine's last launch are rewritten, each by one `prompt_install` launch on the engine's own stream ahead of the
-        program: nothing is re-captured, nobody waits.  Call it with no launch of THIS engine in flight."""
+        program: nothing is re-captured, nobody waits.  Call it with no launch of THIS engine in flight.
+        An entry may be a PromptMix: its slot is then written by one `prompt_mix` launch."""
         self._want_list = list(blks)
         self._want = None
 
@@ -300,16 +304,27 @@ class Engine:
             raise ValueError(f"all frames of a launch must have the same text length, got {[b.layout.tl for b in want]}")
         return want
 
-    def _seg_table(self, src, dst):
+    def _seg_table(self, src, dst, mix: bool = False):
         """(device table, segments) of `prompt_install` for this pair of layouts -- a prompt into a per-frame prompt block, an option entry
-        into a per-frame option block: built once per family"""
-        tabs = self.family.setdefault("seg_tables", {})
+        into a per-frame option block -- or, `mix`, of `prompt_mix` (a mix of prompts into a block of their own layout, or into a per-frame
+        prompt block): built once per family"""
+        tabs = self.family.setdefault("mix_tables" if mix else "seg_tables", {})
         got = tabs.get((src, dst))
         if got is None:
-            segs = (option_segments if isinstance(dst, OptionLayout) else prompt_segments)(src, dst)
+            segs = mix_segments(src, dst) if mix else (option_segments if isinstance(dst, OptionLayout) else prompt_segments)(src, dst)
             got = tabs[(src, dst)] = (self.ops.to_device(torch.tensor(segs, dtype=torch.int64)), len(segs))
             self.ops.synchronize()  # (the other lanes' streams read it too)
+            if mix and hasattr(self.ops, "prompt_mix_table"):
+                self.ops.prompt_mix_table(*got)  # (the library's one-time check of the table, here and not under a frame)
         return got
+
+    def _mix_tables(self, src_layout):
+        """`prepare`: the segment table a PromptMix of prompts of `src_layout` would need for this engine's block, built now, so that the
+        first mix of a stream finds it (no upload, no synchronise under a frame).  Nothing without the op `prompt_mix`."""
+        if hasattr(self.ops, "prompt_mix") and src_layout is not None:
+            tab, nseg = self._seg_table(src_layout, self.pblock.layout, mix=True)
+            if hasattr(self.ops, "prompt_mix_table"):
+                self.ops.prompt_mix_table(tab, nseg)  # (every lane's context checks a table once: this engine's does so here)
 
     def _sync_prompt(self):
         if self.frame_prompts:
@@ -322,10 +337,16 @@ class Engine:
         src = self._want if self._want is not None else self.family.get("prompt")
         if src is None:
             raise RuntimeError("set_text_embeds (or use_prompt) must be called before a launch")
-        if src is not self._installed:
+        if not same_source(src, self._installed):
             if self.pblock is None or src.layout is not self.pblock.layout:
                 raise RuntimeError("the prompt's text length differs from the one this plan was prepared for: prepare again")
-            self.ops.copy_(self.pblock.buf, src.buf)  # one device-to-device copy on this engine's own stream
+            if isinstance(src, PromptMix):  # ONE launch on this engine's own stream in place of the copy
+                if not hasattr(self.ops, "prompt_mix"):
+                    raise ValueError("a prompt mix needs the op prompt_mix, which this ops object does not have")
+                tab, nseg = self._seg_table(src.layout, self.pblock.layout, mix=True)
+                self.ops.prompt_mix([c.buf for c in src.components], src.weights, self.pblock.buf, tab, nseg, 0)
+            else:
+                self.ops.copy_(self.pblock.buf, src.buf)  # one device-to-device copy on this engine's own stream
             self._installed = src
 
     # ---------------------------------------------------------------- per-frame options
@@ -1073,11 +1094,13 @@ class Engine:
             if self.pblock is None or self.pblock.layout is not lay:
                 self.pblock = PromptBlock(self.ops, lay)
                 self._prompt_slots = FrameSlots(self.pblock.buf, lay)
+            self._mix_tables(self._frame_sources(batch)[0].layout)
             return
         src = self._want if self._want is not None else self.family.get("prompt")
         if self.pblock is None or self.pblock.layout is not src.layout:
             self.pblock = PromptBlock(self.ops, src.layout)
             self._installed = self._prompt_slots = None
+        self._mix_tables(src.layout)
 
     def _prepare_constants(self, sched: LCMSchedule, controlnet_scale: float, use_controlnet: bool, ref_mode: bool):
         """Per-plan constants the captured graph reads from device memory: [0:2] add_noise coefficients, [2 + 6i : 8 + 6i]

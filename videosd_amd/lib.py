@@ -15,6 +15,8 @@ SPLITK_MAX_TILES = 16384
 POOL_STREAMS = 4  # include/vsd.h VSD_POOL_STREAMS
 CONV_GROUP_MAX = 8  # include/vsd.h VSD_CONV_GROUP_MAX
 RESAMPLE_MAX_SIDE = 16384  # include/vsd.h VSD_RESAMPLE_MAX_SIDE
+MIX_MAX = 4  # include/vsd.h VSD_MIX_MAX
+MIX_F16, MIX_F32, MIX_COPY = range(3)  # include/vsd.h VSD_MIX_*: the element kind of a vsd_mix_seg
 MERGE_SEG_MAX = 16  # include/vsd.h VSD_MERGE_SEG_MAX
 TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128, TILE_256x128, TILE_256x64, TILE_256x256 = range(7)
 TILE_DIMS = {TILE_128x128: (128, 128), TILE_128x64: (128, 64), TILE_64x64: (64, 64), TILE_64x128: (64, 128),
@@ -114,6 +116,9 @@ SIGNATURES = {
     "vsd_lcm_step_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "vsd_prompt_install": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vsd_prompt_mix_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "vsd_prompt_mix": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vsd_prompt_mix_host": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "vsd_add_noise_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
     "vsd_lcm_step_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,

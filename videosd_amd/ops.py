@@ -776,6 +776,24 @@ class HipOps:
         self.__dict__.setdefault("_seg_tables", {})[segs_dev.data_ptr()] = segs_dev
         self.ctx.call("vsd_prompt_install", self._p(src_buf), self._p(dst_buf), self._p(segs_dev), int(nseg), int(frame), self.raw_stream(0))
 
+    def prompt_mix_table(self, segs_dev, nseg: int):
+        """have the library check the segment table of `prompt_mix` now (one blocking copy) and remember it by address, so that no launch
+        waits for that; segs_dev: int64 [nseg][8] in device memory (blocks.mix_segments).  The table is kept alive here."""
+        self.__dict__.setdefault("_seg_tables", {})[segs_dev.data_ptr()] = segs_dev
+        self.ctx.call("vsd_prompt_mix_table", self._p(segs_dev), int(nseg))
+
+    def prompt_mix(self, src_bufs, weights, dst_buf, segs_dev, nseg: int, frame: int = 0):
+        """a weighted mix of 1..4 cached prompts (their PromptBlock.buf, one layout) into `dst_buf` -- a whole block of that layout, or frame
+        slot `frame` of a per-frame block -- in ONE launch on this object's own stream (include/vsd.h THE PROMPT MIX; csrc/prompt_mix.hip).
+        The sources' addresses and the fp32 weights travel as launch arguments: no upload, no allocation, nobody waits."""
+        n = len(src_bufs)
+        if n != len(weights) or not 1 <= n <= L.MIX_MAX:
+            raise ValueError(f"prompt_mix: {n} source(s) and {len(weights)} weight(s): a mix has 1..{L.MIX_MAX} components, one weight each")
+        self.__dict__.setdefault("_seg_tables", {})[segs_dev.data_ptr()] = segs_dev
+        srcs = (C.c_void_p * n)(*[b.data_ptr() for b in src_bufs])
+        ws = (C.c_float * n)(*[float(w) for w in weights])
+        self.ctx.call("vsd_prompt_mix", srcs, ws, n, self._p(dst_buf), self._p(segs_dev), int(nseg), int(frame), self.raw_stream(0))
+
     # ---- per-frame options (include/vsd.h: strength and ControlNet scale per frame of one launch)
     def add_noise_frames(self, x0, noise_f32, seeds_dev, kind, draw, coef_dev, coef_stride, hw, batch, out):
         """`add_noise_dev` (noise_f32) or `add_noise_seeded` (seeds_dev, kind, draw) -- exactly one of the two -- with image b reading its two

@@ -33,12 +33,17 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-def _finish(w2d: torch.Tensor, bias, cin: int, ksize: int, geglu=False) -> PackedConv:
+def _math(store):
+    """the dtype sums are taken in for weights stored as `store`: fp32 for the product's fp16, fp64 for an fp64 restatement in a test"""
+    return torch.float64 if store == torch.float64 else torch.float32
+
+
+def _finish(w2d: torch.Tensor, bias, cin: int, ksize: int, geglu=False, store=torch.float16) -> PackedConv:
     n, k = w2d.shape
     kp = _round_up(k, 64)
     if kp != k:
         w2d = torch.nn.functional.pad(w2d, (0, kp - k))
-    return PackedConv(w2d.to(torch.float16).contiguous(), None if bias is None else bias.to(torch.float16).contiguous(),
+    return PackedConv(w2d.to(store).contiguous(), None if bias is None else bias.to(store).contiguous(),
                       n, k, kp, cin, ksize, geglu)
 
 
@@ -54,9 +59,9 @@ def pack_conv(weight: torch.Tensor, bias=None, cin_pad: Optional[int] = None) ->
     return _finish(w.reshape(cout, kh * kw * cin), bias, cin, kh)
 
 
-def pack_linear(weight: torch.Tensor, bias=None) -> PackedConv:
+def pack_linear(weight: torch.Tensor, bias=None, store=torch.float16) -> PackedConv:
     assert weight.shape[1] % 8 == 0
-    return _finish(weight, bias, weight.shape[1], 1)
+    return _finish(weight, bias, weight.shape[1], 1, store=store)
 
 
 def pack_linear_cat(weights, biases=None) -> PackedConv:
@@ -79,27 +84,28 @@ def pack_geglu(weight: torch.Tensor, bias: torch.Tensor) -> PackedConv:
     return _finish(w, b, k, 1, geglu=True)
 
 
-def _fold_ln(weight: torch.Tensor, bias, gamma: torch.Tensor, beta: torch.Tensor):
+def _fold_ln(weight: torch.Tensor, bias, gamma: torch.Tensor, beta: torch.Tensor, store=torch.float16):
     """LN(x) W^T + b == rstd * (x (W*gamma)^T - mean * s) + t  with s, t as below.  s is summed over the SAME
     fp16-rounded values the GEMM multiplies with, so that a constant row (x = mean) cancels exactly."""
-    w32, g, b = weight.float(), gamma.float(), beta.float()
-    wp = (w32 * g[None, :]).to(torch.float16)
-    s = wp.float().sum(dim=1)
+    m = _math(store)
+    w32, g, b = weight.to(m), gamma.to(m), beta.to(m)
+    wp = (w32 * g[None, :]).to(store)
+    s = wp.to(m).sum(dim=1)
     t = (w32 * b[None, :]).sum(dim=1)
     if bias is not None:
-        t = t + bias.float()
+        t = t + bias.to(m)
     return wp, s, t
 
 
-def pack_linear_ln(weights, biases, gamma, beta) -> PackedConv:
+def pack_linear_ln(weights, biases, gamma, beta, store=torch.float16) -> PackedConv:
     """Row-concatenated linears that consume LayerNorm(x): the norm is folded into weights + epilogue vectors."""
     w = torch.cat(list(weights), dim=0)
     b = None
     if biases is not None:
         b = torch.cat([bi if bi is not None else torch.zeros(wi.shape[0], dtype=wi.dtype, device=wi.device)
                        for wi, bi in zip(weights, biases)], dim=0)
-    wp, s, t = _fold_ln(w, b, gamma, beta)
-    p = _finish(wp, None, w.shape[1], 1)
+    wp, s, t = _fold_ln(w, b, gamma, beta, store)
+    p = _finish(wp, None, w.shape[1], 1, store=store)
     p.ln_s, p.ln_t = s.contiguous(), t.contiguous()
     return p
 
@@ -122,7 +128,7 @@ def pack_geglu_ln(weight: torch.Tensor, bias: torch.Tensor, gamma, beta) -> Pack
 
 
 def pack_cross_attention(k: torch.Tensor, v: torch.Tensor, wq: torch.Tensor, wo: torch.Tensor, bo, gamma, beta, heads: int,
-                         group: int = 128):
+                         group: int = 128, dtype=torch.float16):
     """Cross-attention over a FIXED key set (the text tokens) as two plain GEMMs ("absorbed" form).
 
         out = Concat_h[ softmax(scale * q_h K_h^T) V_h ] Wo^T + bo,   q = LN(x) Wq^T
@@ -135,21 +141,24 @@ def pack_cross_attention(k: torch.Tensor, v: torch.Tensor, wq: torch.Tensor, wo:
     (PackedConv G' with ln_s / ln_t: N = heads*group, K = C;  PackedConv Z with bias: N = C, K = heads*group).  The first
     GEMM runs with the VSD_ACT_SOFTMAX epilogue (softmax_cols = tl), the second is an ordinary linear layer with the
     residual in its epilogue.  One head per 128-column tile: C >= heads*group/2 keeps the FLOP count at or below the
-    three-kernel form (q projection, attention, out projection); the engine uses it for C >= 640."""
+    three-kernel form (q projection, attention, out projection); the engine uses it for C >= 640.
+    dtype: what the packed tensors are stored in.  torch.float64 (tests: the algebra without the product's fp16 rounding) also takes every
+    sum in fp64."""
     tl, c = k.shape
     dh = c // heads
     assert tl <= group and c % heads == 0
-    kf, vf, wqf, wof = k.float(), v.float(), wq.float(), wo.float()
+    m = _math(dtype)
+    kf, vf, wqf, wof = k.to(m), v.to(m), wq.to(m), wo.to(m)
     scale = dh ** -0.5
-    g = torch.zeros(heads * group, c, dtype=torch.float32)
-    z = torch.zeros(c, heads * group, dtype=torch.float32)
+    g = torch.zeros(heads * group, c, dtype=m)
+    z = torch.zeros(c, heads * group, dtype=m)
     for h in range(heads):
         sl = slice(h * dh, (h + 1) * dh)
         g[h * group:h * group + tl] = scale * (kf[:, sl] @ wqf[sl, :])
         z[:, h * group:h * group + tl] = wof[:, sl] @ vf[:, sl].t()
-    xa1 = pack_linear_ln([g], None, gamma, beta)
+    xa1 = pack_linear_ln([g], None, gamma, beta, store=dtype)
     xa1.tile128 = True
-    xa2 = pack_linear(z, bo)
+    xa2 = pack_linear(z, bo, store=dtype)
     return xa1, xa2
 
 

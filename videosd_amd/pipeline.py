@@ -24,6 +24,7 @@ from PIL import Image
 
 from . import config as C
 from . import checkpoints as CK
+from . import promptmix as PM
 from . import weights as W
 from .frames import I420Frame, is_i420
 from .lcm import lcm_timesteps
@@ -73,8 +74,8 @@ def load_or_synthesize(spec, prefix: str, filename: str, device, snapshot_file: 
 
 
 def _prompt_key(prompt):
-    """what the prompt cache (and an SDXL plan) knows a prompt by: the string, or the list as a tuple"""
-    return prompt if isinstance(prompt, str) else tuple(prompt)
+    """what the prompt cache (and an SDXL plan) knows a prompt by: the string, the list as a tuple, the canonical form of a mix"""
+    return PM.prompt_key(prompt)
 
 
 class PlanKey(NamedTuple):
@@ -180,6 +181,7 @@ class VideoSDPipeline:
         self.is_xl, self.unet_cfg, self.model, self.text_encoder, self.weight_sources, self._xl_prompts = False, C.SD15_UNET, None, None, {}, {}  # (`load_model`)
         self._ref_img, self._ref_epoch = None, 0
         self._prompts, self._plans, self.evictions = OrderedDict(), OrderedDict(), 0
+        self.prompt_builds = 0  # `Engine.build_prompt` calls of the prompt cache (a mix of cached prompts causes none)
         self._in_flight: List[Launch] = []  # submitted, not yet collected
         self._host_ms = {k: [] for k in ("crop_resize", "upload_enqueue", "wait_download", "to_pil", "to_i420", "gpu", "prepare", "update_options", "prompt")}
         self._io_bytes = {"up": None, "down": None}  # per frame of the last launch submitted / collected
@@ -309,7 +311,8 @@ class VideoSDPipeline:
 
     def _prompts_in_use(self):
         """ids of the cache entries a launch in flight on a `frame_prompts` engine reads (its installs may not have executed yet)"""
-        return {id(b) for h in self._in_flight for b in (h.engine._prompt_slots.src if h.engine._prompt_slots is not None else ()) if b is not None}
+        srcs = [b for h in self._in_flight for b in (h.engine._prompt_slots.src if h.engine._prompt_slots is not None else ()) if b is not None]
+        return {id(c) for b in srcs for c in getattr(b, "components", (b,))}  # (a slot that holds a mix reads the mix's components)
 
     def _cache_prompt(self, key, embeds=None, prompt=None, keep=()):
         """The block of prompt `key`, built from `embeds` or from the text `prompt` when the cache lacks it (or holds other embeddings).  Over
@@ -327,6 +330,7 @@ class VideoSDPipeline:
             t0 = time.perf_counter()
             blk = self.model.build_prompt(embeds if embeds is not None else self.encode_prompt(prompt))
             self._prompts[key] = blk
+            self.prompt_builds += 1
             self._note("prompt", t0)
             if len(self._prompts) > max(1, self.max_prompts):
                 busy = self._prompts_in_use()
@@ -382,6 +386,7 @@ class VideoSDPipeline:
         out["plans_cached"] = len(self._engines)
         out["programs_cached"] = len(self._plans)
         out["prompts_cached"] = len(self._prompts)
+        out["prompt_builds"] = self.prompt_builds
         out["engines_evicted_for_memory"] = self.evictions
         free, total = torch.cuda.mem_get_info(int(self.device))  # what a leak across plan / prompt changes would show in
         return {"stage_ms_p50": out, "io_bytes_per_frame": dict(self._io_bytes), "device_free_mb": free >> 20, "device_total_mb": total >> 20,
@@ -421,7 +426,10 @@ class VideoSDPipeline:
         """Same contract as videopipeline.py:75-128.  `guidance_scale`, `ref`, `style_fidelity` and
         `controlnet` are accepted and ignored exactly like the reference (ControlNet always runs; 7.5 is baked
         in); `seed` does not change the result because the reference resets the CPU generator state per frame -- unless the
-        object was built with `device_seed=True`: then the frame's noise is a function of `seed` (include/vsd.h)."""
+        object was built with `device_seed=True`: then the frame's noise is a function of `seed` (include/vsd.h).
+        `prompt`: a string or a one-element list as in the reference, or a weighted mix of up to four texts as JSON-able data,
+        `{"mix": [["text a", 0.3], ["text b", 0.7]]}` (promptmix.py has the rules): the engine blends the CACHED constants of the texts on the
+        device in one small launch (include/vsd.h THE PROMPT MIX), so a prompt slider or a fade costs no prompt build and no cache entry."""
         return self.infer_batch([img], prompt=prompt, height=height, width=width, strength=strength, steps=steps,
                                 guidance_scale=guidance_scale, ref=ref, style_fidelity=style_fidelity,
                                 controlnet=controlnet, seed=seed, controlnet_scale=controlnet_scale)[0]
@@ -469,10 +477,10 @@ class VideoSDPipeline:
         imgs, raw, i420, yuv, height, width = self._launch_frames(imgs, width, height, ref)
         self._note("crop_resize", t0)
         if plist is not None:  # one cache entry per frame (the same object for equal prompts)
-            keys = [_prompt_key(p) for p in plist]
-            pblock = [self._cache_prompt(k, prompt=p, keep=keys) for k, p in zip(keys, plist)]
+            keys = [_prompt_key(c) for p in plist for c in PM.component_prompts(p)]
+            pblock = [self._prompt_source(p, keys) for p in plist]
         else:
-            pblock = self._cache_prompt(_prompt_key(prompt), prompt=prompt)  # cached: nothing to do; new: ~1 ms on the GPU, nobody waits
+            pblock = self._prompt_source(prompt)  # cached: nothing to do; new: ~1 ms on the GPU, nobody waits
         key, pairs = self._launch_options(imgs, raw, strength, controlnet_scale,
                                           dict(prompt=prompt, height=height, width=width, steps=steps, ref=ref, controlnet=controlnet))
         seeds = self._launch_seeds(seed, len(imgs))
@@ -487,19 +495,37 @@ class VideoSDPipeline:
         self._note("upload_enqueue", t0)
         return handle
 
+    def _prompt_source(self, prompt, keep=()):
+        """What an engine takes for `prompt` (canonical): the cache entry of a text, or a PromptMix of the cache entries of a mix's texts.
+        Each component goes through the prompt cache; the mix itself never enters it and is never built or encoded."""
+        if not isinstance(prompt, PM.Mix):
+            return self._cache_prompt(_prompt_key(prompt), prompt=prompt, keep=keep)
+        from .blocks import PromptMix
+
+        keep = tuple(keep) + prompt.texts  # (no component evicts another)
+        return PromptMix([self._cache_prompt(t, prompt=t, keep=keep) for t in prompt.texts], prompt.weights)
+
     def _launch_prompts(self, n: int, prompt, prompts, ref):
-        """Phase 1 -> (the launch's `prompt`, one prompt per frame or None in the one-prompt-per-launch mode)."""
+        """Phase 1 -> (the launch's `prompt`, one prompt per frame or None in the one-prompt-per-launch mode), every prompt in its canonical
+        form (promptmix.canonical: a mix that is not one is refused here, a mix of one component is that text)."""
         plist = None
+        prompt = PM.canonical(prompt)
+        if self.is_xl and isinstance(prompt, PM.Mix):
+            raise ValueError("prompt: a mix of more than one component is not possible here: an SDXL program has the pooled text embedding "
+                             "of ITS prompt baked in")
         if prompts is not None:
             if not self.frame_prompts:
                 raise ValueError("prompts= (one prompt per frame) needs a pipeline built with frame_prompts=True; this one runs one prompt per launch (`prompt`)")
-            plist = list(prompts)
+            plist = [PM.canonical(p) for p in prompts]
             if len(plist) != n:
                 raise ValueError(f"prompts must hold one prompt per frame: {len(plist)} prompt(s) for {n} frame(s)")
         elif self.frame_prompts:
             plist = [prompt] * n
         if plist is None:
             return prompt, None
+        if self.is_xl and any(isinstance(p, PM.Mix) for p in plist):
+            raise ValueError("prompts: a mix of more than one component is not possible here: an SDXL program has the pooled text embedding "
+                             "of ITS prompt baked in")
         if len({_prompt_key(p) for p in plist}) > 1 and (self.is_xl or (bool(ref) and self.honor_ref_flag)):
             raise ValueError("prompts: more than one distinct prompt in a launch is not possible here: " +
                              ("an SDXL program has the pooled text embedding of ITS prompt baked in" if self.is_xl else
@@ -797,6 +823,9 @@ class VideoSDPipeline:
         if self.edges != "sobel":
             raise ValueError(f'export_plan: this pipeline was built with edges="{self.edges}"; its programs call vsd_canny_control, which is not a '
                              'plan function: export from a pipeline built with edges="sobel" (the default)')
+        if isinstance(PM.canonical(options.get("prompt", INFER_DEFAULTS["prompt"])), PM.Mix):
+            raise ValueError("export_plan: `prompt` is a mix; a plan file holds ONE cached prompt's constants and the C library forms no mix "
+                             "for a plan (vsd_prompt_mix is not a plan function): export with one of the texts")
         self._require_idle("export a plan")
         w, h = int(options.get("width", INFER_DEFAULTS["width"])), int(options.get("height", INFER_DEFAULTS["height"]))
         imgs = [Image.new("RGB", (w, h), (127, 127, 127)) for _ in range(int(frames_per_launch))]
@@ -808,6 +837,9 @@ class VideoSDPipeline:
         """Another prompt's constants as a file for vsd_plan_load_prompt (a loaded plan takes it without a new plan)."""
         from .plan import export_prompt
 
+        if isinstance(PM.canonical(prompt), PM.Mix):
+            raise ValueError("export_prompt: `prompt` is a mix; a prompt file holds ONE cached prompt's constants (it does not say which of its "
+                             "bytes are fp16, fp32 or independent of the prompt, so the C side could not mix two of them): export the texts")
         return export_prompt(self._cache_prompt(_prompt_key(prompt), prompt=prompt), path)
 
     def set_tuning_mode(self, mode: str):
