@@ -6,6 +6,7 @@ server.py:104-143), one worker process per GPU, frames sharded round-robin, drop
   python examples/frame_loop.py --gpus 1 --fps 60 --seconds 10 --batch 3          (needs the MI355X)
   python examples/frame_loop.py --factory helpers_fake_pipeline:FakePipeline ...   (any stand-in with the same surface)
   python examples/frame_loop.py --fade-to "a charcoal sketch" --fade-frames 60 ...  (a cross-fade between two prompts, written as 60 mixes)
+  python examples/frame_loop.py --color-match histogram:0.8 ...   (every output frame keeps its camera frame's colours, matched on the device)
 
 Prints one JSON line: frames offered / processed / dropped, output frames per second, p50 / p95 submit->result latency.
 """
@@ -44,6 +45,9 @@ def crossfade(a: str, b: str, k: int, frames: int):
 async def run(args):
     cfg = dict(model=args.model, controlnet=args.controlnet)
     extra = json.loads(args.worker_config) if args.worker_config else {}
+    if args.color_match:  # MODE[:AMOUNT] -> the constructor's color_match / color_amount (fixed mode; `set_color_match` moves the amount live)
+        mode, _, amount = args.color_match.partition(":")
+        extra.update(color_match=mode, color_amount=float(amount) if amount else 1.0)
     workers = [RemotePipeline(factory=args.factory, batch=args.batch, device=i, **cfg, **extra) for i in range(args.gpus)]
     opts = dict(prompt=args.prompt, height=args.height, width=args.width, strength=args.strength, steps=args.steps,
                 controlnet_scale=args.controlnet_scale, seed=23)
@@ -108,6 +112,8 @@ def main(argv=None):
     ap.add_argument("--prompt", default="pixar, cg")
     ap.add_argument("--fade-to", dest="fade_to", default="", help="cross-fade from --prompt to this prompt, as prompt mixes")
     ap.add_argument("--fade-frames", dest="fade_frames", type=int, default=60, help="frames the cross-fade takes")
+    ap.add_argument("--color-match", dest="color_match", default="", metavar="MODE[:AMOUNT]",
+                    help="histogram or meanstd, and an amount in [0, 1] (default 1): transfer each camera frame's colours onto its output frame")
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--strength", type=float, default=0.6)

@@ -52,7 +52,7 @@ enum vsd_family {
   VSD_FAM_ATTENTION = 4, VSD_FAM_ELEMENTWISE = 5, VSD_FAM_COUNT = 6
 };
 
-/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds; vsd_prompt_install joined version 10 without a bump: plan files do not change, and a library without the symbol is refused by name at load; so did the three vsd_canny_* entry points) and the size in
+/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds; vsd_prompt_install joined version 10 without a bump: plan files do not change, and a library without the symbol is refused by name at load; so did the three vsd_canny_* and the three vsd_color_match* entry points) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
 #define VSD_VERSION 10
@@ -516,6 +516,51 @@ int64_t vsd_canny_workspace_bytes(int h, int w);
 int vsd_canny_control(vsd_ctx* ctx, const void* rgb_u8, int h, int w, int low, int high, void* edge_u8, void* control_out, void* workspace,
                       void* stream);
 int vsd_canny_host(const void* rgb_u8, int h, int w, int low, int high, void* edge_u8);
+
+/* ---- Colour match: the input frame's colour distribution onto the output frame, on the device (csrc/color_match.hip, ----------------
+ * csrc/color_match_core.h).  TAESD desaturates and a 2-4 step LCM shifts the white point with the prompt, differently from frame to
+ * frame; video tools cure that by transferring the camera frame's colours onto the restyled frame ("colour coherence", ColorMatch).
+ * The reference has no such stage; here it is opt-in and the default program does not change.
+ * THE COLOUR CONTRACT (fixed; device kernels, the host twin and the tests are held to it byte for byte):
+ *   inputs      src and dst: packed u8 [h][w][3], any alignment; sides 1..VSD_RESAMPLE_MAX_SIDE and N = h*w <= VSD_COLOR_MAX_PIXELS
+ *               (2^23: the bound the 64-bit products below need); mode VSD_COLOR_HIST or VSD_COLOR_MEANSTD; amount: an integer a in
+ *               0..256.  dst is rewritten in place; src is only read.
+ *   histograms  per channel c, Hs[c][v] and Hd[c][v], v = 0..255: exact counts of the value v in src and in dst.
+ *   matched value m_c(v), per channel, for v = 0..255:
+ *     HIST      Cs[u], Cd[v]: inclusive prefix sums of Hs[c], Hd[c].  m(v) = the smallest u with 2*Cs[u] >= 2*Cd[v] - Hd[v] (the rank
+ *               of the MIDDLE of dst's run of v: a constant dst maps to src's median, not to its maximum).  Cs[255] = N >= Cd[v], so u
+ *               exists; 2*N <= 2^24: every integer stays below 2^32.
+ *     MEANSTD   S = sum v*H[v], Q = sum v*v*H[v] of either histogram, in 64 bits.  Vs = N*Qs - Ss*Ss, Vd = N*Qd - Sd*Sd (N^2 times the
+ *               variances, so >= 0).  N*Q and S*S are at most N^2 * 255^2 <= 2^46 * 65025 < 2^62: below 2^63 -- that product is what
+ *               limits N; with both sides at VSD_RESAMPLE_MAX_SIDE it would reach 2^72.
+ *               g = (Vd == 0) ? 0 : min(sqrt((double)Vs / (double)Vd), 4.0)
+ *               m(v) = clamp(floor(((double)Ss + g * (double)((int64)N*v - (int64)Sd)) / (double)N + 0.5), 0, 255)
+ *               Every conversion is exact (Ss < 2^31, |N*v - Sd| < 2^32) except those of Vs and Vd, which round to nearest even;
+ *               every fp64 operation (/, sqrt, *, +, /, +) is rounded on its own, to nearest even, never contracted into an fma.
+ *   amount      lut_c[v] = (v*(256 - a) + m_c(v)*a + 128) >> 8: a = 0 is the identity byte for byte, a = 256 is m.
+ *   apply       dst[p][c] = lut_c[dst[p][c]].
+ *   A value that dst does not hold has a LUT entry all the same (it is never read).  With src == dst (the same bytes) both modes leave
+ *   dst as it is: HIST because the middle of a run lies inside the run, MEANSTD because g = 1 makes the quotient exactly v.
+ * vsd_color_match: `frames` frames per call, frame f at src_u8 + f*3*N and dst_u8 + f*3*N (so frame bases fall on any byte offset);
+ *   amounts_dev: int32 [frames] in DEVICE memory, 4-byte aligned, read by the kernels when they run (a captured graph holds the pointer,
+ *   not the values; a value outside 0..256 is clamped into it).  workspace: >= vsd_color_match_workspace_bytes(frames, h, w) bytes,
+ *   16-byte aligned, contents on entry do not matter; it carries the partial histograms and the LUTs between the launches, so two calls
+ *   in flight at once need a workspace each.  Always three launches on `stream`, whatever the frames hold: (1) histograms -- every
+ *   workgroup counts a contiguous span of one frame into LDS and stores its partial [6][256]; (2) one workgroup per frame sums the
+ *   partials and builds the 3 x 256 LUT; (3) apply.  No global atomics, no memset, no host synchronisation; capturable; the result is
+ *   a function of the operands alone, bit for bit the same on every run.  frames 1..VSD_COLOR_MAX_FRAMES.
+ * vsd_color_match_host: one frame by the contract as plain host loops; no GPU and no context (VSD_ERR_ARG without a message; here an
+ *   amount outside 0..256 is refused).
+ * Not a plan function: a program that records it has no plan-file export; a C host applies vsd_color_match_host to the frame a plan
+ *   returns, or vsd_color_match to device buffers of its own. */
+#define VSD_COLOR_HIST 0
+#define VSD_COLOR_MEANSTD 1
+#define VSD_COLOR_MAX_PIXELS (1 << 23)
+#define VSD_COLOR_MAX_FRAMES 1024
+int64_t vsd_color_match_workspace_bytes(int frames, int h, int w);
+int vsd_color_match(vsd_ctx* ctx, const void* src_u8, void* dst_u8, int frames, int h, int w, int mode, const void* amounts_dev, void* workspace,
+                    void* stream);
+int vsd_color_match_host(const void* src_u8, void* dst_u8, int h, int w, int mode, int amount);
 
 /* ---- two independent operations as ONE grid per kernel ------------------------------------------------
  * The reference runs the ControlNet and then the UNet encoder of a denoising step -- the same topology with two weight sets on the

@@ -5,7 +5,8 @@ import collections, csv, json, sys
 trace, opsf = sys.argv[1], sys.argv[2]
 ops = json.load(open(opsf))
 ours = ("conv_gemm_kernel", "conv_gemm8_kernel", "conv_gemm_group_kernel", "conv_halo_kernel", "conv_c64", "tail_kernel", "adain_kernel", "splitk_reduce", "gn_stats", "gn_apply", "gn_fused", "layernorm_kernel", "attention_kernel", "attention_lazy", "attention_pair", "attention_lazy", "attention_pair",
-        "preprocess_rgb", "sobel_max", "sobel_apply", "canny_tile", "canny_border", "canny_mark", "canny_write", "add_noise", "lcm_step", "postprocess")
+        "preprocess_rgb", "sobel_max", "sobel_apply", "canny_tile", "canny_border", "canny_mark", "canny_write", "add_noise", "lcm_step", "postprocess",
+        "color_hist", "color_lut", "color_apply")
 rows = [r for r in csv.DictReader(open(trace)) if any(o in r["Kernel_Name"] for o in ours)]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last eager frame = everything from the last preprocess_rgb kernel on
@@ -16,7 +17,7 @@ agg = collections.OrderedDict()
 busy = 0
 total = 0
 for m in ops:
-    n = {"groupnorm": 2, "sobel_control": 2, "canny_control": 4}.get(m["op"], 1)
+    n = {"groupnorm": 2, "sobel_control": 2, "canny_control": 4, "color_match": 3}.get(m["op"], 1)
     if m["op"] in ("conv", "conv_group") and pos + 1 < len(last) and "splitk_reduce" in last[pos + 1]["Kernel_Name"]:
         n = 2
     if m["op"] == "groupnorm" and "gn_stats" not in last[pos]["Kernel_Name"]:

@@ -743,6 +743,7 @@ class RemotePipeline:
         self.infer = _RemoteMethod(self, "infer")
         self.compile_model = _RemoteMethod(self, "compile_model")
         self.set_prompt_embeds = _RemoteMethod(self, "set_prompt_embeds")
+        self.set_color_match = _RemoteMethod(self, "set_color_match")
         self.sync_prompt = _RemoteMethod(self, "__sync_prompt__")
         self.sync_tuning = _RemoteMethod(self, "__sync_tuning__")
         self.join_group = _RemoteMethod(self, "__join_group__")

@@ -184,6 +184,11 @@ class Engine:
         self.edge_u8 = None          # ... its edge map(s)
         self.edges = None            # what `edge_u8` and the ControlNet's conditioning hold: "sobel" (the reference's stand-in) or "canny"
         self.canny_thresholds = None  # `edges="canny"`: (low, high), integers on |dx| + |dy|
+        self.color_mode = None       # the colour-match stage behind `postprocess_rgb`: None, "histogram" or "meanstd"
+        self.color_amounts = None    # ... its amounts on the device, int32 [B] (0..256): the program reads them when it runs
+        self._color_host = None      # ... their pinned mirror
+        self.color_a = None          # ... what the next launch runs with: a tuple of B integers (`set_color_amount`)
+        self._color_sent = None      # ... and what `color_amounts` holds (`_sync_color`)
         self.ref_u8 = None           # `ref_mode`: the reference image
         self._ref_epoch = None       # ... and which reference image of the pipeline `ref_u8` holds (VideoSDPipeline sets it)
         self.noise = None            # the host draws on the device (None: `device_seed`)
@@ -989,7 +994,7 @@ class Engine:
     def prepare(self, H: int, W: int, steps: int, strength: float, controlnet_scale: float = 1.0,
                 use_controlnet: bool = True, use_graph: Optional[bool] = None, autotune: bool = True, batch: int = 1,
                 ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False, frame_options: bool = False,
-                edges: str = "sobel", canny_thresholds=(100, 200)):
+                edges: str = "sobel", canny_thresholds=(100, 200), color_match: Optional[str] = None, color_amount=1.0):
         """Fix the frame geometry and schedule; build the static program and capture it into a hipGraph
         (the reference's intent at videopipeline.py:35-47, `compile_model`).
 
@@ -1026,10 +1031,22 @@ class Engine:
         control_v11p_sd15_canny was trained on; the program records `canny_control` in place of `sobel_control`, call for call.
         canny_thresholds = (low, high): integers with 0 <= low <= high <= 2040 on |dx| + |dy| (floats are floored), read by "canny" only.
         Composes with every other mode (none of them touches the edge stage); without a ControlNet there is no edge stage and the
-        switch is inert.  A "canny" program has no plan-file export (`vsd_canny_control` is not a plan function)."""
+        switch is inert.  A "canny" program has no plan-file export (`vsd_canny_control` is not a plan function).
+
+        color_match: None (default: the program as before, call for call), "histogram" or "meanstd": the colours of every input frame
+        are transferred onto its output frame by THE COLOUR CONTRACT of include/vsd.h -- the program records one `color_match` over
+        all B frames right behind `postprocess_rgb`, from `frame_u8` onto `out_u8` in place.  color_amount: a number in [0, 1] (0: the
+        output as it is, 1: fully matched), the value every frame starts with; `set_color_amount` changes it per frame from the next launch on
+        without a re-capture.  Composes with every other mode (the source is whatever ended up in `frame_u8`; ref_mode and SDXL
+        included).  Such a program has no plan-file export (`vsd_color_match` is not a plan function)."""
         edges, canny_thresholds = L.check_edges(edges, canny_thresholds)
         if edges == "canny" and not hasattr(self.ops, "canny_control"):
             raise ValueError('edges="canny" needs the op canny_control, which this ops object does not have')
+        color_match, color_a = L.check_color_match(color_match, color_amount)
+        if color_match is not None and not hasattr(self.ops, "color_match"):
+            raise ValueError(f'color_match="{color_match}" needs the op color_match, which this ops object does not have')
+        if color_match is not None and H * W > L.COLOR_MAX_PIXELS:
+            raise ValueError(f'color_match="{color_match}": a {W} x {H} frame has more than {L.COLOR_MAX_PIXELS} pixels (include/vsd.h VSD_COLOR_MAX_PIXELS)')
         self._check_arguments(H, W, batch, use_controlnet, ref_mode, device_seed, frame_prompts, frame_options)
         sched = LCMSchedule(strength, steps)
         self._prepare_prompt_block(batch, frame_prompts)
@@ -1039,6 +1056,11 @@ class Engine:
         self.batch = batch
         self.frame_prompts, self.frame_options = bool(frame_prompts), bool(frame_options)
         self.edges, self.canny_thresholds = edges, canny_thresholds if edges == "canny" else None
+        self.color_mode = color_match
+        if color_match is not None:  # (this engine's own, like the seeds: a slot has its own)
+            self.color_amounts = self.ops.zeros(batch, dtype=torch.int32)
+            self._color_host = torch.zeros(batch, dtype=torch.int32, pin_memory=torch.cuda.is_available())
+            self.set_color_amount(color_a / L.COLOR_MAX_AMOUNT)
         # The lock-step encoders are the one-stream form of EVERY program.  What a pair's grid looks like depends on the mode: a one-frame
         # program (latency mode) takes the pair's own table entry, timed alone; a coalesced launch on busy lanes (throughput mode) runs
         # the pair in the form its members have as launches of their own -- a latency-chosen form there occupies more workgroup-time
@@ -1055,6 +1077,7 @@ class Engine:
         self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=len(sched), batch=batch,
                          ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), frame_options=bool(frame_options), tuned_for_lanes=bool(self.tune_for_lanes),
                          edge_mode=self.edges, canny_thresholds=self.canny_thresholds,  # ("edges" is taken: the event edges of the captured sequence)
+                         color_match=self.color_mode,
                          sizes=self._level_sizes(H, W), timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=self.arena.peak)
         self._warm_up_and_capture(autotune)
         return self.plan
@@ -1266,6 +1289,8 @@ class Engine:
             sops.lcm_step(r, eps, cur, i + 1 if sched.multistep else 0, c[2 + 6 * i:8 + 6 * i], B, nxt, den, dec_in if last else None)
         self._decode(r, dec_in, h0, w0, dec_out)
         r.postprocess_rgb(dec_out, 8, B * H * W, out_b)
+        if self.color_mode is not None:  # ahead of everything that reads `out_u8` (`collect_u8`, the queued `rgb_to_i420`)
+            r.color_match(frame_b, out_b, B, H, W, self.color_mode, self.color_amounts)
         # program: what a lone launch runs (the ControlNet encoder on the side stream when `overlap_controlnet`);
         # program_serial: everything on the lane's own stream (the encoders in lock step when `twin_encoders`)
         self.program = r.flavor(0 if self.overlap_controlnet or not self._twin_now else 1)
@@ -1277,6 +1302,7 @@ class Engine:
         torch.cuda.synchronize() if torch.cuda.is_available() else None  # allocation fills vs. kernel streams
         self._sync_prompt()
         self._sync_options()
+        self._sync_color()
         if autotune:  # (only shapes missing from the shared table are timed: a slot with the parent's batch size finds all)
             self.autotune()
         self.program.run()
@@ -1342,6 +1368,26 @@ class Engine:
         self.plan.update(strength=strength, cn_scale=controlnet_scale, timesteps=sched.timesteps)
         return True
 
+    def set_color_amount(self, amount):
+        """The colour-match amount of the launches from the next one on: a number in [0, 1] for every frame, or one per frame of the
+        launch.  Only noted here (a launch in flight keeps the amounts it was submitted with); `launch` sends a changed value ahead of
+        the program (`_sync_color`), as the seeds travel: no re-capture, no drain."""
+        if self.color_amounts is None:
+            raise ValueError("set_color_amount needs an engine prepared with color_match=\"histogram\" or \"meanstd\"")
+        B = self.color_amounts.numel()
+        vals = list(amount) if isinstance(amount, (list, tuple, np.ndarray)) else [amount] * B
+        if len(vals) != B:
+            raise ValueError(f"color_amount must be a number or a sequence of {B} numbers (one per frame of the launch)")
+        self.color_a = tuple(L.check_color_amount(v) for v in vals)
+
+    def _sync_color(self):
+        """the amounts of `set_color_amount` on the lane's stream ahead of the program, when they changed: 4 bytes per frame from the pinned
+        mirror (the lane's previous launch has been collected, so nothing in flight reads the mirror)"""
+        if self.color_a != self._color_sent:
+            self._color_host.numpy()[:] = np.array(self.color_a, dtype=np.int32)
+            self.ops.upload(self.color_amounts, self._color_host)
+            self._color_sent = self.color_a
+
     @staticmethod
     def host_noise(n_steps: int, h: int, w: int, ref: bool = False):
         """The CPU draws of one frame, in the reference's order: draw 0 = prepare_latents noise
@@ -1376,6 +1422,7 @@ class Engine:
         (lane + 2 mod 4) may be in flight -- two busy queues on one command-processor pipe take turns (ops.HipOps)."""
         self._sync_prompt()
         self._sync_options()
+        self._sync_color()
         if self.graph is not None:
             ov = self.overlap_launch if overlap is None else overlap
             self.ops.seq_launch(self.graph if ov else self.graph_serial)

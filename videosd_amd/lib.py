@@ -2,6 +2,7 @@
 fails, a RuntimeError is raised."""
 import ctypes as C
 import math
+import numbers
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,6 +40,26 @@ def check_edges(edges, canny_thresholds):
     if not 0 <= low <= high <= CANNY_MAX_MAG:
         raise ValueError(f"canny_thresholds must satisfy 0 <= low <= high <= {CANNY_MAX_MAG} (integers on |dx| + |dy|), not {canny_thresholds!r}")
     return edges, (int(low), int(high))
+
+
+COLOR_MODES = {"histogram": 0, "meanstd": 1}  # include/vsd.h VSD_COLOR_HIST, VSD_COLOR_MEANSTD; None: no colour-match stage
+COLOR_MAX_AMOUNT = 256      # include/vsd.h THE COLOUR CONTRACT: the amount is an integer a in 0..256
+COLOR_MAX_PIXELS = 1 << 23  # include/vsd.h VSD_COLOR_MAX_PIXELS
+
+
+def check_color_amount(amount) -> int:
+    """a colour-match amount, a number in [0, 1] -> the contract's integer a = round(amount * 256) in 0..COLOR_MAX_AMOUNT"""
+    if isinstance(amount, bool) or not isinstance(amount, numbers.Real) or not 0.0 <= amount <= 1.0:  # (a NaN fails the comparison)
+        raise ValueError(f"color_amount must be a number in [0, 1], not {amount!r}")
+    return int(math.floor(float(amount) * COLOR_MAX_AMOUNT + 0.5))
+
+
+def check_color_match(mode, amount=1.0):
+    """-> (mode, a) as `Engine.prepare` and `VideoSDPipeline` take them, checked against THE COLOUR CONTRACT of include/vsd.h: `mode`
+    None (no stage) or one of COLOR_MODES; `amount` a number in [0, 1] -> the integer a = round(amount * 256)."""
+    if mode is not None and mode not in COLOR_MODES:
+        raise ValueError(f'color_match must be None, "histogram" or "meanstd", not {mode!r}')
+    return mode, check_color_amount(amount)
 
 
 class ConvDesc(C.Structure):
@@ -145,6 +166,9 @@ SIGNATURES = {
     "vsd_canny_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "vsd_canny_control": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vsd_canny_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vsd_color_match_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "vsd_color_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vsd_color_match_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vsd_graph_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vsd_graph_end": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "vsd_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

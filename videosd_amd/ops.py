@@ -736,6 +736,15 @@ class HipOps:
         self.ctx.call("vsd_canny_control", self._p(rgb_u8), int(h), int(w), int(low), int(high), self._p(edge_u8), self._p(control_out),
                       self._p(ws), self.s)
 
+    def color_match(self, src_u8, dst_u8, frames, h, w, mode, amounts_dev):
+        """The colours of `src_u8` onto `dst_u8` in place, `frames` packed [h][w][3] frames each, by THE COLOUR CONTRACT of include/vsd.h
+        (csrc/color_match.hip).  mode: a key of lib.COLOR_MODES; amounts_dev: int32 [frames] in device memory, the contract's integer
+        amounts 0..256, read when the kernels run (a captured graph follows a later copy into it).  Three launches; the workspace carries
+        the partial histograms and the LUTs between them: it is this object's, keyed like "canny" by the scratch set of the stream in use."""
+        ws = self.workspace("color_match", int(self.ctx.lib.vsd_color_match_workspace_bytes(int(frames), int(h), int(w))))
+        self.ctx.call("vsd_color_match", self._p(src_u8), self._p(dst_u8), int(frames), int(h), int(w), int(L.COLOR_MODES[mode]),
+                      self._p(amounts_dev), self._p(ws), self.s)
+
     def add_noise(self, x0, noise_f32, sqrt_a, sqrt_b, hw, out):
         self.ctx.call("vsd_add_noise", self._p(x0), self._p(noise_f32), sqrt_a, sqrt_b, hw, self._p(out), self.s)
 

@@ -28,7 +28,7 @@ from . import promptmix as PM
 from . import weights as W
 from .frames import I420Frame, is_i420
 from .lcm import lcm_timesteps
-from .lib import RESAMPLE_MAX_SIDE, check_edges
+from .lib import COLOR_MAX_AMOUNT, RESAMPLE_MAX_SIDE, check_color_amount, check_color_match, check_edges
 
 
 def center_crop_resize(img: Image.Image, width: int, height: int) -> Image.Image:
@@ -157,6 +157,13 @@ class VideoSDPipeline:
             Default edges="sobel": the reference's stand-in (canny_gpu.py:27-44), the same programs and bits as before.  Fixed for the life
             of the object; composes with every switch above; such a pipeline has no `export_plan`.  SDXL has no ControlNet tower: there
             the switch is accepted and inert.
+        color_match="histogram" | "meanstd", color_amount=1.0: the colours of every input frame (after crop / resize / I420 conversion: what
+            the model sees) are transferred onto its output frame on the device, inside the captured program, by THE COLOUR CONTRACT of
+            include/vsd.h -- per channel, by histogram matching or by mean and standard deviation -- and blended with the unmatched
+            output by `color_amount` in [0, 1]: the cure video tools call colour coherence, against TAESD's desaturation and the
+            frame-to-frame colour flicker of a few-step LCM.  Default None: no such stage, the same programs and bits as before.  The mode
+            is fixed for the life of the object; `set_color_match(amount)` changes the amount live (no re-capture; a worker collects its launches in flight first).  Composes with every
+            switch above, with I420 frames, reference-only mode and SDXL; such a pipeline has no `export_plan`.
         lanes: launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on launch
             stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch.
         tuning_mode: "auto": shapes missing from the table are timed on this GPU at `prepare`; "table": never -- they take the deterministic
@@ -173,6 +180,7 @@ class VideoSDPipeline:
         for switch in ("honor_controlnet_flag", "honor_ref_flag", "device_resize", "device_seed", "frame_prompts", "frame_options"):
             setattr(self, switch, bool(kwargs.get(switch, False)))
         self.edges, self.canny_thresholds = check_edges(kwargs.get("edges", "sobel"), kwargs.get("canny_thresholds", (100, 200)))
+        self.color_match, self._color_a = check_color_match(kwargs.get("color_match"), kwargs.get("color_amount", 1.0))
         self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
         self.tuning_mode = str(kwargs.get("tuning_mode", "auto"))
         self.max_prompts = int(kwargs.get("max_prompts", 8))
@@ -347,6 +355,19 @@ class VideoSDPipeline:
         self._require_idle("change the reference image")
         self._ref_img = img
         self._ref_epoch += 1
+
+    def set_color_match(self, amount: float) -> float:
+        """The colour-match amount, a number in [0, 1], of every launch submitted from now on (`color_match=` of the constructor chose
+        the mode).  Every cached engine takes it on its own stream ahead of its next launch (`Engine.set_color_amount`): no
+        re-capture, and launches in flight keep the amount they were submitted with.  Called on this object nothing waits; through a
+        worker (`VideoSDPipeline.remote(...).set_color_match`) the call runs alone like every method but `infer`, so the worker first
+        collects the launches it has in flight."""
+        if self.color_match is None:
+            raise ValueError('set_color_match needs a pipeline built with color_match="histogram" or "meanstd"')
+        self._color_a = check_color_amount(amount)
+        return self.color_amount
+
+    color_amount = property(lambda self: self._color_a / COLOR_MAX_AMOUNT, doc="the colour-match amount in [0, 1], as the contract rounds it")
 
     def option_class(self, options) -> int:
         """What two requests must share to run in ONE launch of a `frame_options` pipeline although their `strength` / `controlnet_scale`
@@ -613,6 +634,8 @@ class VideoSDPipeline:
         eng.use_prompts(pblock) if isinstance(pblock, list) else eng.use_prompt(pblock)
         if key.frame_options:
             eng.use_options(pairs)
+        if self.color_match is not None and set(eng.color_a) != {self._color_a}:  # (`set_color_match` since this engine's last launch)
+            eng.set_color_amount(self.color_amount)
         if key.use_ref and eng._ref_epoch != self._ref_epoch:
             rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), key.width, key.height), dtype=np.uint8)
             eng.ops.upload(eng.ref_u8, torch.from_numpy(np.array(rf, copy=True)))  # (PIL's buffer is read-only)
@@ -755,6 +778,8 @@ class VideoSDPipeline:
         mode = {k: True for k in ("device_seed", "frame_prompts", "frame_options") if getattr(plan_key, k)}  # (the default mode, and stand-ins: none)
         if self.edges != "sobel":  # (not in the plan key: constant for the life of this object)
             mode.update(edges=self.edges, canny_thresholds=self.canny_thresholds)
+        if self.color_match is not None:  # (likewise)
+            mode.update(color_match=self.color_match, color_amount=self.color_amount)
         eng.prepare(plan_key.height, plan_key.width, plan_key.steps, strength, controlnet_scale=cn_scale, use_controlnet=plan_key.use_cn,
                     batch=batch, ref_mode=plan_key.use_ref, autotune=self.tuning_mode != "table", **mode)
         plan.engines[(batch, lane)] = eng
@@ -823,6 +848,9 @@ class VideoSDPipeline:
         if self.edges != "sobel":
             raise ValueError(f'export_plan: this pipeline was built with edges="{self.edges}"; its programs call vsd_canny_control, which is not a '
                              'plan function: export from a pipeline built with edges="sobel" (the default)')
+        if self.color_match is not None:
+            raise ValueError(f'export_plan: this pipeline was built with color_match="{self.color_match}"; its programs call vsd_color_match, which is '
+                             'not a plan function: export from a pipeline built with color_match=None (the default)')
         if isinstance(PM.canonical(options.get("prompt", INFER_DEFAULTS["prompt"])), PM.Mix):
             raise ValueError("export_plan: `prompt` is a mix; a plan file holds ONE cached prompt's constants and the C library forms no mix "
                              "for a plan (vsd_prompt_mix is not a plan function): export with one of the texts")

@@ -238,6 +238,9 @@ def export_plan(engine, path: str) -> dict:
     if engine.plan.get("edge_mode", "sobel") != "sobel":
         raise ValueError(f'export_plan: this engine was prepared with edges="{engine.plan["edge_mode"]}"; its program calls vsd_canny_control, which is not a '
                          'plan function: export the plan of an engine prepared with edges="sobel" (the default)')
+    if engine.plan.get("color_match") is not None:
+        raise ValueError(f'export_plan: this engine was prepared with color_match="{engine.plan["color_match"]}"; its program calls vsd_color_match, which is '
+                         'not a plan function: export the plan of an engine prepared with color_match=None (the default)')
     ops.synchronize()
     calls = []
 
