@@ -77,7 +77,9 @@ const char* vsd_last_error(vsd_ctx* ctx);
  * act == GEGLU: weights/bias are tile-packed (64 hidden + 64 gate rows per 128-row tile); the output
  * has n/2 columns: out[m][j] = (h_j + b) * gelu_erf(g_j + b).
  * Columns >= t_col0 (when out_t != NULL) are written TRANSPOSED to out_t[(n - t_col0) * ldt + m]
- * (this is how the attention V operand is produced as V^T).                                        */
+ * (this is how the attention V operand is produced as V^T).  Transposed columns take bias, rowvec,
+ * the activation and out_scale, no residual; act | VSD_ACT_POST together with out_t is refused
+ * (VSD_ERR_ARG): there is no residual for the activation to follow.                                */
 typedef struct vsd_conv_desc {
   const void* src0;
   const void* src1;       /* second concat source or NULL */

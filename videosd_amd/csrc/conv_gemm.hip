@@ -123,6 +123,9 @@ static int conv_setup(vsd_ctx* ctx, const vsd_conv_desc* d, ConvLaunch& cl, bool
   if ((p.act & 0xff) == VSD_ACT_GELU && (p.out_t || p.rowstat_out || p.ln_part || (p.act & VSD_ACT_POST)))
     return vsd_fail(ctx, VSD_ERR_ARG, "conv_gemm: erf GELU exists in the general epilogue walk only (no transposed output, row statistics, "
                     "fused LayerNorm or post-residual form)");
+  if (p.out_t && (p.act & VSD_ACT_POST))
+    return vsd_fail(ctx, VSD_ERR_ARG, "conv_gemm: an activation after the residual (VSD_ACT_POST) does not exist with a transposed output "
+                    "(the transposed columns take no residual and would get no activation at all)");
   if (p.rowstat_out && (p.N % 64 || p.out_t || (p.split_k > 1 && !d->counters)))
     return vsd_fail(ctx, VSD_ERR_ARG, "conv_gemm: rowstat_out needs N %% 64 == 0, no transposed output and the in-kernel split-K form");
   if (p.chanstat_out && (!p.chanstat_part || !p.chan_counters || p.N % 8 || p.out_t || (p.act & 0xff) == VSD_ACT_GEGLU ||
