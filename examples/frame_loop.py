@@ -45,6 +45,15 @@ def crossfade(a: str, b: str, k: int, frames: int):
 async def run(args):
     cfg = dict(model=args.model, controlnet=args.controlnet)
     extra = json.loads(args.worker_config) if args.worker_config else {}
+    if args.lora:  # PATH[:SCALE], up to four -> the constructor's loras (`set_lora_scale(name, value)` moves a scale live)
+        loras = []
+        for item in args.lora:
+            path, sep, scale = item.rpartition(":")
+            try:
+                loras.append({"path": path, "scale": float(scale)} if sep else {"path": item})
+            except ValueError:
+                loras.append({"path": item})
+        extra.update(loras=loras)
     if args.color_match:  # MODE[:AMOUNT] -> the constructor's color_match / color_amount (fixed mode; `set_color_match` moves the amount live)
         mode, _, amount = args.color_match.partition(":")
         extra.update(color_match=mode, color_amount=float(amount) if amount else 1.0)
@@ -112,6 +121,8 @@ def main(argv=None):
     ap.add_argument("--prompt", default="pixar, cg")
     ap.add_argument("--fade-to", dest="fade_to", default="", help="cross-fade from --prompt to this prompt, as prompt mixes")
     ap.add_argument("--fade-frames", dest="fade_frames", type=int, default=60, help="frames the cross-fade takes")
+    ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
+                    help="a LoRA adapter file (safetensors) fused on the device at SCALE (default 1.0); up to four")
     ap.add_argument("--color-match", dest="color_match", default="", metavar="MODE[:AMOUNT]",
                     help="histogram or meanstd, and an amount in [0, 1] (default 1): transfer each camera frame's colours onto its output frame")
     ap.add_argument("--height", type=int, default=512)

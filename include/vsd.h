@@ -52,7 +52,7 @@ enum vsd_family {
   VSD_FAM_ATTENTION = 4, VSD_FAM_ELEMENTWISE = 5, VSD_FAM_COUNT = 6
 };
 
-/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds; vsd_prompt_install joined version 10 without a bump: plan files do not change, and a library without the symbol is refused by name at load; so did the three vsd_canny_* and the three vsd_color_match* entry points) and the size in
+/* Version of this interface (bumped whenever a struct grows or an entry point is added; round 3 = 3, round 4 = 4, round 5 = 5: pipeline 8 -- the stream-K form -- left the library; round 6 = 6: pipelines 8 / 9 / 10, vsd_groupnorm_launches, vsd_plan_*; 7: vsd_resample_*, vsd_plan_infer_frame; 9: vsd_plan_set_options, vsd_plan_clone_lane, vsd_plan_memory, vsd_lcm_timesteps, plan files of format 2; 10: vsd_noise_fill, vsd_add_noise_seeded, vsd_lcm_step_seeded, vsd_plan_set_seeds; vsd_prompt_install joined version 10 without a bump: plan files do not change, and a library without the symbol is refused by name at load; so did the three vsd_canny_* and the three vsd_color_match* entry points; and the four vsd_lora_* entry points of THE ADAPTER FUSE) and the size in
  * bytes of vsd_conv_desc as the LIBRARY was built: a caller compares both with its own header before the first call
  * (videosd_amd/lib.py does) instead of passing a short struct to a stale libvsd.so. */
 #define VSD_VERSION 10
@@ -356,6 +356,65 @@ int vsd_prompt_mix(vsd_ctx* ctx, const void* const* src_blocks, const float* wei
                    int nseg, int frame, void* stream);
 int vsd_prompt_mix_host(const void* const* src_blocks, const float* weights, int n, void* dst_block, const vsd_mix_seg* segs, int nseg,
                         int frame);
+
+/* ---- THE ADAPTER FUSE: LoRA adapters fused into the packed weights on the device (csrc/lora.hip, csrc/lora_core.h) --------------------
+ * For ONE weight matrix of the checkpoint: W0 the base matrix, fp16 [rows][K] (a conv weight in the packed order k = (ky, kx, c), the
+ * input channels padded as pack_conv pads them); adapters i = 0 .. n-1, n <= VSD_LORA_MAX, each with down_i fp16 [r_i][K] (a conv
+ * adapter's down matrix permuted and padded like W0, once at load), up_i fp16 [rows][r_i], 1 <= r_i <= VSD_LORA_MAX_RANK, a constant
+ * a_i = fp32(alpha_i / r_i) from the file (alpha = r without an alpha key) and a live scale s_i = scales[slot_i], fp32, a launch
+ * argument (slot_i: which of the engine's up to four adapters this is; strictly increasing within a segment).
+ * ELEMENT ARITHMETIC, per (row, k), every operation fp32 and rounded to nearest even on its own:
+ *     d_i = 0.0f;  for j = 0 .. r_i-1 in order:  d_i = d_i + float(up_i[row][j]) * float(down_i[j][k])
+ *     acc = float(W0[row][k]);  for i in order, where s_i != 0:  acc = fadd(acc, fmul(fmul(s_i, a_i), d_i))
+ *     Wf  = fp16(acc)
+ *   The product of two fp16 values is exact in fp32, so a rank step rounds once whether or not it is an fma.  An adapter whose scale is
+ *   exactly 0 is SKIPPED, not multiplied by zero: with every scale zero Wf is W0 bit for bit (a -0 stays -0), whatever the adapter holds.
+ * WHERE Wf GOES is what packing.py does to a checkpoint weight.  dr = row0 + map(row): map is the identity (VSD_LORA_MAP_ID) or the
+ *   GEGLU tile map of pack_geglu (VSD_LORA_MAP_GEGLU, rows % 128 == 0: with f = rows / 2, row < f goes to 128 * (row / 64) + row % 64,
+ *   row >= f to 128 * ((row - f) / 64) + 64 + (row - f) % 64).
+ *   Plain destination (gamma == NULL): dst[dr][k] = Wf, leading dimension kp halfs.  The pad columns K <= k < kp are not touched.
+ *   LayerNorm-folded destination (gamma, beta fp32 [K], ln_s, ln_t fp32 indexed by dr; pack_linear_ln, pack_geglu_ln):
+ *     dst[dr][k] = wp = fp16(fmul(float(Wf), gamma[k]));  ln_s[dr] = SUM_k float(wp);  ln_t[dr] = SUM_k fmul(float(Wf), beta[k]), and
+ *     where bias != NULL (fp32 [rows], indexed by row) ln_t[dr] = fadd(that sum, bias[row]).
+ *   THE ORDER OF THE TWO SUMS: 64 partials p_0 .. p_63, each 0.0f; the 16-byte chunk c (k = 8c .. 8c+7) belongs to partial c mod 64;
+ *     a partial adds its elements one by one in increasing k (p = fadd(p, x)); then the fixed tree
+ *     for h = 32, 16, 8, 4, 2, 1:  p_l = fadd(p_l, p_{l+h}) for l < h;  the sum is p_0.  (On the device a partial is a lane of the wave
+ *     that owns the row; no atomics.)
+ *   Second copy (copy != NULL): VSD_LORA_COPY_RAW: copy[row][k] = Wf, fp16 [rows][K] (the raw to_q of an absorbed block);
+ *     VSD_LORA_COPY_FRAG: what went to dst[dr][k], in the fragment-major layout of pack_mfma_frag over [N][K]: the half at
+ *     ((((dr / 16) * (K / 32) + k / 32) * 4 + (k % 32) / 8) * 16 + dr % 16) * 8 + k % 8  (K % 32 == 0, rows % 16 == 0, row0 % 16 == 0).
+ * vsd_lora_fuse: ONE launch on `stream` over a table of nseg segments in DEVICE memory (16-byte aligned); scales: four floats on the
+ *   HOST, launch arguments: a scale change uploads nothing.  A table is read back and checked when the context first sees it (one
+ *   blocking copy) and must not change afterwards; vsd_lora_fuse_table does that check alone, and with nseg = 0 forgets the table.
+ *   16-byte vector stores.  Nothing that reads the destinations may be in flight: the caller's to ensure.
+ * vsd_lora_fuse_host: the same arithmetic, orders and addressing as plain host loops over HOST memory; no GPU, no context.
+ * VSD_ERR_ARG with a reason, before anything is launched or written: nseg outside 1..65535; a scale that is not finite; in a segment a
+ *   null or misaligned pointer (16 bytes for w0, dst, down, copy, gamma, beta; 4 for bias, ln_s, ln_t; 2 for up), rows outside
+ *   1..2^24, K outside 8..2^20 or no multiple of 8, kp < K or no multiple of 8, row0 < 0, n outside 1..VSD_LORA_MAX, a rank outside
+ *   1..VSD_LORA_MAX_RANK, slots not strictly increasing within 0..3, an a_i that is not finite, an unknown map or copy kind or one whose
+ *   divisibility conditions fail, gamma without beta, ln_s and ln_t, or reserved != 0.  The buffers' SIZES and that no two segments
+ *   write the same bytes are the caller's. */
+#define VSD_LORA_MAX 4
+#define VSD_LORA_MAX_RANK 128
+enum { VSD_LORA_MAP_ID = 0, VSD_LORA_MAP_GEGLU = 1 };
+enum { VSD_LORA_COPY_NONE = 0, VSD_LORA_COPY_RAW = 1, VSD_LORA_COPY_FRAG = 2 };
+typedef struct vsd_lora_seg {
+  const void* w0;
+  void* dst;
+  int64_t rows, k, kp, row0;
+  int32_t map, n, copy_kind, reserved;
+  const void* up[VSD_LORA_MAX];
+  const void* down[VSD_LORA_MAX];
+  int32_t rank[VSD_LORA_MAX], slot[VSD_LORA_MAX];
+  float a[VSD_LORA_MAX];
+  const float *gamma, *beta, *bias;
+  float *ln_s, *ln_t;
+  void* copy;
+} vsd_lora_seg;
+int vsd_lora_seg_size(void);
+int vsd_lora_fuse_table(vsd_ctx* ctx, const vsd_lora_seg* segs_dev, int nseg);
+int vsd_lora_fuse(vsd_ctx* ctx, const vsd_lora_seg* segs_dev, int nseg, const float* scales, void* stream);
+int vsd_lora_fuse_host(const vsd_lora_seg* segs, int nseg, const float* scales);
 
 /* ---- per-frame options: strength and ControlNet scale per frame of one launch (csrc/noise.hip, csrc/norm.hip, csrc/frame_options.hip) ----
  * `strength` decides the timesteps (scheduler coefficients, time embeddings) and `controlnet_scale` the 13 residual scales.  The default

@@ -161,6 +161,7 @@ class OptionEntry:
 
     def __init__(self, layout: OptionLayout, buf, timesteps):
         self.layout, self.buf, self.timesteps = layout, buf, tuple(timesteps)
+        self.sched, self.cn, self.epoch = None, True, 0  # what `Engine._fill_option_entry` rebuilds it from, and the "weights_epoch" it was built under
 
 
 def schedule_constants(sched: LCMSchedule) -> List[float]:
@@ -189,6 +190,7 @@ class PromptBlock:
         self.buf = ops.zeros(layout.nbytes, dtype=torch.uint8)  # zero: V^T key padding and the unused rows of the xa weights
         self._xa = {}
         self.text = None
+        self.epoch = 0  # the family's "weights_epoch" (LoRA scale changes) the constants were built under
 
     def view(self, ni, bi, name):
         off, shape, dtype = self.layout.items[(ni, bi, name)]

@@ -60,6 +60,7 @@ struct vsd_ctx {
   std::unordered_map<const void*, std::pair<int, int>> prompt_tables;  // vsd_prompt_install: table -> (segments, frame slots), once checked
   std::unordered_map<const void*, std::pair<int, int>> mix_tables;     // vsd_prompt_mix: table -> (segments, frame slots), once checked
   std::unordered_map<const void*, std::pair<int, int>> merge_tables;   // vsd_cn_merge_frames: table -> (segments, largest scale column), once checked
+  std::unordered_map<const void*, int> lora_tables;                    // vsd_lora_fuse: table -> segments, once checked
 };
 
 static inline int vsd_fail(vsd_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));

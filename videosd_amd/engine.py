@@ -18,6 +18,7 @@ Data layout in HBM
 """
 import copy
 import os
+import weakref
 from collections import OrderedDict
 from typing import Dict, Optional
 
@@ -159,6 +160,7 @@ class Engine:
         self._want = None           # `use_prompt`: this engine's prompt (None: the family default)
         self._want_list = None      # `use_prompts`: one PromptBlock per frame of the launch (None: `_want` / the default for every frame)
         self._prompt_slots = None   # FrameSlots of a per-frame `pblock` (`prepare(frame_prompts=True)`): the PromptBlock each slot holds
+        self._prompt_epoch = 0      # the family's "weights_epoch" (`set_adapter_scales`) that `_installed` / `_prompt_slots` were written under
         # device memory and pinned host memory that is reused from plan to plan
         self._vt_pool = {}          # (C, columns, index) -> zero-padded V^T buffer of a self-attention, outside the rewound arena
         self._stage = None          # (shape, pinned frame in, pinned frame out, event before the launch, event after it): `_staging`
@@ -255,6 +257,13 @@ class Engine:
         self.family["layout"] = lay
         blk = PromptBlock(ops, lay)
         blk.text = text
+        self._fill_prompt(blk)
+        return blk
+
+    def _fill_prompt(self, blk: PromptBlock):
+        """the constants of `blk.text` under the weights as they are now, into `blk` (a fresh block, or one built before a LoRA scale change)"""
+        ops, lay, text = self.ops, blk.layout, blk.text
+        tl = lay.tl
         for ni, net in enumerate(self._nets()):
             for bi, t in enumerate(net.transformers):
                 c = t.kv2.n // 2
@@ -267,7 +276,7 @@ class Engine:
                                    blk.view(ni, bi, "xa1_s"), blk.view(ni, bi, "xa1_t"), blk.view(ni, bi, "xa2_w"))
                     ops.copy_(blk.view(ni, bi, "xa2_b"), t.out2.bias)
         ops.synchronize()
-        return blk
+        blk.epoch = self.family.get("weights_epoch", 0)
 
     def set_text_embeds(self, embeds: torch.Tensor):
         """The prompt of this engine AND of every engine made from it that was not given one of its own (`use_prompt`).
@@ -331,7 +340,37 @@ class Engine:
             if hasattr(self.ops, "prompt_mix_table"):
                 self.ops.prompt_mix_table(tab, nseg)  # (every lane's context checks a table once: this engine's does so here)
 
+    def _sync_weights(self):
+        """Ahead of a launch, after a LoRA scale change (`set_adapter_scales` moved the family's "weights_epoch"): everything derived from
+        the UNet's weights outside the packed buffers is stale.  (a) The time tables the plan reads (`shared["temb"]`: time_embedding,
+        cond_proj and every time_emb_proj) are written again by the first engine that launches from this `shared`; (b) option entries of a
+        `frame_options` plan and (c) cached prompts (kv2, out2, to_q) are rebuilt IN PLACE, from their stored schedule / text embeddings,
+        before their next use; (d) what this engine had installed of either is forgotten.  Nothing happens without adapters."""
+        ep = self.family.get("weights_epoch", 0)
+        if ep == 0 and self.family.get("adapters") is None:
+            return
+        sh = self.shared
+        if not self.frame_options and "sched" in sh and sh.get("weights_epoch", 0) != ep:
+            self._write_time_tables(sh["sched"], sh["sched_cn"])
+        if ep != self._prompt_epoch:
+            self._installed = None
+            for slots in (self._prompt_slots, self._option_slots):
+                if slots is not None:
+                    slots.src = [None] * len(slots.src)
+            self._prompt_epoch = ep
+        for ent, _c in self._want_opts or ():
+            if ent.epoch != ep:
+                self._fill_option_entry(ent)
+        sources = self._want_list if self._want_list is not None else [self._want if self._want is not None else self.family.get("prompt")]
+        for src in sources:
+            for b in (src.components if isinstance(src, PromptMix) else (src,)):
+                if b is not None and b.epoch != ep:
+                    if b.text is None:
+                        raise RuntimeError("a prompt block without its text embeddings cannot follow a LoRA scale change: build it with build_prompt")
+                    self._fill_prompt(b)
+
     def _sync_prompt(self):
+        self._sync_weights()
         if self.frame_prompts:
             want = self._frame_sources(self.batch)
             lay = self.pblock.layout
@@ -353,6 +392,58 @@ class Engine:
             else:
                 self.ops.copy_(self.pblock.buf, src.buf)  # one device-to-device copy on this engine's own stream
             self._installed = src
+
+    # ---------------------------------------------------------------- LoRA adapters (include/vsd.h THE ADAPTER FUSE)
+    def _family_idle(self, what: str):
+        n = len(self.family.get("in_flight", ()))
+        if n:
+            raise RuntimeError(f"cannot {what} while {n} launch(es) of this family of engines are in flight: collect them first")
+
+    def load_adapters(self, adapters, w_unet):
+        """adapters: 1..4 lora.Adapter (lora.load_adapter / lora.parse_adapter); w_unet: the checkpoint dict this family's UNet was built
+        from (the base copies are taken from it, for the tensors some adapter touches and no others).  Builds the base copies and the
+        segment table once; every scale starts at 0, so nothing changes until `set_adapter_scales`.  The ControlNet is never adapted.
+        A checkpoint that lives on the device is aliased by the packed buffers whose layout needs no change, so a later fuse rewrites
+        those entries of `w_unet` in place: the base copies are taken here, before that, and `w_unet` is not looked at again."""
+        from .lora import AdapterSet
+
+        if self.family.get("adapters") is not None:
+            raise RuntimeError("adapters are loaded already: unload_adapters() first")
+        if not hasattr(self.ops, "lora_fuse"):
+            raise ValueError("LoRA adapters need the op lora_fuse, which this ops object does not have")
+        self._family_idle("load adapters")
+        aset = AdapterSet(self.ops, self.unet, w_unet, adapters)
+        self.ops.lora_fuse_table(aset.table, aset.nseg)
+        self.family["adapters"] = aset
+        return aset
+
+    def set_adapter_scales(self, scales):
+        """One launch on this engine's stream: every adapted tensor's fused weight from its base copy, straight into the packed buffers the
+        recorded programs read by address -- nothing is re-captured, no plan is lost.  Always computed from the base copies: no drift, no
+        dependence on the scales before.  The weights are shared by every engine of the family, so none of them may have a launch in
+        flight.  Time tables, option entries and cached prompts follow lazily (`_sync_weights`)."""
+        aset = self.family.get("adapters")
+        if aset is None:
+            raise RuntimeError("no adapters are loaded: load_adapters first")
+        sc = tuple(float(x) for x in scales)
+        if len(sc) != len(aset.adapters) or not all(np.isfinite(x) for x in sc):
+            raise ValueError(f"set_adapter_scales: {len(aset.adapters)} finite scale(s) wanted, one per loaded adapter, got {list(scales)!r}")
+        self._family_idle("change a LoRA scale")
+        self.ops.lora_fuse(aset.table, aset.nseg, sc)
+        if not any(sc):
+            aset.restore_fold(self.ops)
+        self.ops.synchronize()  # (the other lanes' streams read these weights)
+        aset.scales = sc
+        self.family["weights_epoch"] = self.family.get("weights_epoch", 0) + 1
+
+    def unload_adapters(self):
+        """the load-time bytes back (a fuse with every scale zero, the fold vectors by copy), then the base copies and the table freed"""
+        aset = self.family.get("adapters")
+        if aset is None:
+            return
+        self.set_adapter_scales((0.0,) * len(aset.adapters))
+        self.ops.lora_fuse_table(aset.table, 0)
+        self.family["adapters"] = None
 
     # ---------------------------------------------------------------- per-frame options
     def _nres(self) -> int:
@@ -380,16 +471,25 @@ class Engine:
             host = torch.zeros(lay.coef_stride, dtype=torch.float32)
             host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
             self.ops.upload(lay.view(buf, "coef"), host)
-            for name, net in self._networks(use_controlnet):
-                self._time_embeddings(net, sched, lay.view(buf, name))
-            self.ops.synchronize()  # (the other lanes' streams read it too)
             ent = cache[key] = OptionEntry(lay, buf, key[0])
+            ent.sched, ent.cn = sched, bool(use_controlnet)
+            self._fill_option_entry(ent)
             self.family["option_builds"] = self.family.get("option_builds", 0) + 1
             while len(cache) > max(1, int(self.family.get("max_option_entries", MAX_OPTION_ENTRIES))):
                 cache.popitem(last=False)  # least recently used first; an engine (or a launch's handle) that still holds it keeps it alive
         else:
             cache.move_to_end(key)
+            if ent.epoch != self.family.get("weights_epoch", 0):  # built before a LoRA scale change
+                self._fill_option_entry(ent)
         return ent
+
+    def _fill_option_entry(self, ent: OptionEntry):
+        """the time tables of an option entry from the weights as they are now (a fresh entry, or IN PLACE one built before a LoRA scale
+        change: the family is idle then, and every engine installs it again)"""
+        for name, net in self._networks(ent.cn):
+            self._time_embeddings(net, ent.sched, ent.layout.view(ent.buf, name))
+        self.ops.synchronize()  # (the other lanes' streams read it too)
+        ent.epoch = self.family.get("weights_epoch", 0)
 
     def use_options(self, pairs):
         """`frame_options` engines: frame i of this engine's launches runs with pairs[i] = (strength, controlnet_scale) from the next launch
@@ -1344,11 +1444,18 @@ class Engine:
         host = torch.zeros(c.numel(), dtype=torch.float32)
         host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
         self.ops.upload(c, host)
+        self._write_time_tables(sched, use_controlnet)
+
+    def _write_time_tables(self, sched: LCMSchedule, use_controlnet: bool):
+        """the per-step time-embedding projections of the plan(s) that share `shared`, from the weights as they are NOW; remembers the
+        schedule and the family's "weights_epoch", so that the first launch after a LoRA scale change can write them again"""
         for name, net in self._networks(use_controlnet):
             self._time_embeddings(net, sched, self.shared["temb"][name])
         if self.shared.get("ref_mode"):  # the reference-only WRITE pass: same timesteps, no guidance embedding
             self._time_embeddings(self.unet, sched, self.shared["temb"]["ref"], use_cond=False)
         self.ops.synchronize()
+        self.shared["sched"], self.shared["sched_cn"] = sched, bool(use_controlnet)
+        self.shared["weights_epoch"] = self.family.get("weights_epoch", 0)
 
     def update_options(self, strength: float, controlnet_scale: float) -> bool:
         """New `strength` / `controlnet_scale` for the prepared plan WITHOUT re-capturing: the captured graph reads the
@@ -1486,6 +1593,7 @@ class Engine:
         if e0 is not None:
             e0.record(self.ops.stream)
         self.launch(overlap)
+        self.family.setdefault("in_flight", weakref.WeakSet()).add(self)  # (until the collect: what `set_adapter_scales` must not run beside; an engine that is dropped uncollected leaves by itself)
         if e1 is not None:
             e1.record(self.ops.stream)
 
@@ -1637,6 +1745,7 @@ class Engine:
         one = H * W * 3 // 2
         _, _hin, _hout, e0, e1 = self._staging()
         self.ops.download_into(host, dev)
+        self.family.get("in_flight", set()).discard(self)
         self.last_download_bytes = B * one
         if e0 is not None:
             self.last_gpu_ms = e0.elapsed_time(e1)  # the graph alone, as `collect_u8` reports it
@@ -1653,6 +1762,7 @@ class Engine:
         want = self._want_shape()
         _, _hin, hout, e0, e1 = self._staging()
         self.ops.download_into(hout, self.out_u8)
+        self.family.get("in_flight", set()).discard(self)
         if e0 is not None:
             self.last_gpu_ms = e0.elapsed_time(e1)  # the graph alone (between the H2D and the D2H copies)
         return hout.numpy().reshape(want).copy()

@@ -19,6 +19,10 @@ RESAMPLE_MAX_SIDE = 16384  # include/vsd.h VSD_RESAMPLE_MAX_SIDE
 MIX_MAX = 4  # include/vsd.h VSD_MIX_MAX
 MIX_F16, MIX_F32, MIX_COPY = range(3)  # include/vsd.h VSD_MIX_*: the element kind of a vsd_mix_seg
 MERGE_SEG_MAX = 16  # include/vsd.h VSD_MERGE_SEG_MAX
+LORA_MAX = 4  # include/vsd.h VSD_LORA_MAX: adapters loaded at once
+LORA_MAX_RANK = 128  # include/vsd.h VSD_LORA_MAX_RANK
+LORA_MAP_ID, LORA_MAP_GEGLU = range(2)  # include/vsd.h VSD_LORA_MAP_*
+LORA_COPY_NONE, LORA_COPY_RAW, LORA_COPY_FRAG = range(3)  # include/vsd.h VSD_LORA_COPY_*
 TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128, TILE_256x128, TILE_256x64, TILE_256x256 = range(7)
 TILE_DIMS = {TILE_128x128: (128, 128), TILE_128x64: (128, 64), TILE_64x64: (64, 64), TILE_64x128: (64, 128),
              TILE_256x128: (256, 128), TILE_256x64: (256, 64), TILE_256x256: (256, 256)}
@@ -92,6 +96,20 @@ class ConvDesc(C.Structure):
     ]
 
 
+class LoraSeg(C.Structure):
+    """include/vsd.h vsd_lora_seg: one weight matrix of THE ADAPTER FUSE"""
+    _fields_ = [
+        ("w0", C.c_void_p), ("dst", C.c_void_p),
+        ("rows", C.c_int64), ("k", C.c_int64), ("kp", C.c_int64), ("row0", C.c_int64),
+        ("map", C.c_int32), ("n", C.c_int32), ("copy_kind", C.c_int32), ("reserved", C.c_int32),
+        ("up", C.c_void_p * LORA_MAX), ("down", C.c_void_p * LORA_MAX),
+        ("rank", C.c_int32 * LORA_MAX), ("slot", C.c_int32 * LORA_MAX), ("a", C.c_float * LORA_MAX),
+        ("gamma", C.c_void_p), ("beta", C.c_void_p), ("bias", C.c_void_p),
+        ("ln_s", C.c_void_p), ("ln_t", C.c_void_p),
+        ("copy", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/vsd.h
 SIGNATURES = {
     "vsd_version": (C.c_int, []),
@@ -140,6 +158,10 @@ SIGNATURES = {
     "vsd_prompt_mix_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "vsd_prompt_mix": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vsd_prompt_mix_host": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "vsd_lora_seg_size": (C.c_int, []),
+    "vsd_lora_fuse_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "vsd_lora_fuse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_void_p]),
+    "vsd_lora_fuse_host": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "vsd_add_noise_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_void_p]),
     "vsd_lcm_step_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -236,6 +258,8 @@ def load():
         fn.argtypes = args
     # same interface version and the same vsd_conv_desc layout on both sides of the boundary (the struct grew
     # three fields while vsd_version stayed 1; a stale library was only caught through missing symbols)
+    if lib.vsd_lora_seg_size() != C.sizeof(LoraSeg):
+        raise RuntimeError(f"{rebuild} (library: vsd_lora_seg {lib.vsd_lora_seg_size()} bytes; this binding: {C.sizeof(LoraSeg)} bytes)")
     if lib.vsd_version() != VERSION or lib.vsd_conv_desc_size() != C.sizeof(ConvDesc):
         raise RuntimeError(f"{rebuild} (library: interface version {lib.vsd_version()}, vsd_conv_desc {lib.vsd_conv_desc_size()} bytes; "
                            f"this binding: version {VERSION}, {C.sizeof(ConvDesc)} bytes)")

@@ -10,6 +10,21 @@ from .weights import skip_channels
 
 
 @dataclass
+class Place:
+    """Where one checkpoint weight landed in the kernel-layout buffers: what THE ADAPTER FUSE (include/vsd.h) needs to write a fused weight
+    over it.  `pack.weight` rows [row0, row0 + rows) (through `geglu`'s tile map), columns [0, pack.k)."""
+    pack: PackedConv
+    rows: int
+    row0: int = 0
+    geglu: bool = False                 # rows go through the GEGLU tile map of packing.pack_geglu
+    cin_pad: Optional[int] = None       # a conv: k = (ky, kx, c) with c padded to this (None: as in the checkpoint)
+    fold: Optional[tuple] = None        # (gamma, beta) of the LayerNorm folded in (checkpoint tensors): pack.ln_s / pack.ln_t follow the weight
+    fold_bias: Optional[torch.Tensor] = None  # ... and the bias packing._fold_ln adds to ln_t
+    raw_copy: Optional[torch.Tensor] = None   # a second copy of the raw fp16 weight [rows][k] (BlockW.xa_raw[0])
+    frag: bool = False                  # pack.weight_frag is a second, fragment-major copy of pack.weight
+
+
+@dataclass
 class ResnetW:
     cin: int
     cout: int
@@ -63,6 +78,8 @@ class NetWeights:
         self._temb_w, self._temb_b = [], []
         self._temb_cols = 0
         self.transformers: List[BlockW] = []  # every BasicTransformerBlock, in kv_cache order
+        self.places: Dict[str, Place] = {}    # checkpoint name of every kind-"w" weight -> where it landed (host-side bookkeeping only)
+        self._temb_names = []
         dev = ops.to_device
         ch = cfg.block_out_channels
         self.conv_in = self._conv("conv_in", cin_pad=8)
@@ -121,6 +138,8 @@ class NetWeights:
         # all per-ResnetBlock time projections as ONE linear layer: [sum Cout][temb_dim]
         tw = pack_linear_cat(self._temb_w, self._temb_b)
         self.temb_proj = self._to_dev(tw)
+        for name, off, rows in self._temb_names:
+            self.places[name] = Place(self.temb_proj, rows, row0=off)
         self._w = None
         self._temb_w = self._temb_b = None
 
@@ -134,10 +153,14 @@ class NetWeights:
 
     def _conv(self, name, cin_pad=None, with_bias=True) -> PackedConv:
         b = self._w.get(name + ".bias") if with_bias else None
-        return self._to_dev(pack_conv(self._w[name + ".weight"], b, cin_pad=cin_pad))
+        p = self._to_dev(pack_conv(self._w[name + ".weight"], b, cin_pad=cin_pad))
+        self.places[name + ".weight"] = Place(p, p.n, cin_pad=cin_pad)
+        return p
 
     def _lin(self, name) -> PackedConv:
-        return self._to_dev(pack_linear(self._w[name + ".weight"], self._w.get(name + ".bias")))
+        p = self._to_dev(pack_linear(self._w[name + ".weight"], self._w.get(name + ".bias")))
+        self.places[name + ".weight"] = Place(p, p.n)
+        return p
 
     def _norm(self, name):
         return (self.ops.to_device(self._w[name + ".weight"].half().contiguous()),
@@ -146,6 +169,7 @@ class NetWeights:
     def _resnet(self, p, cin, cout) -> ResnetW:
         off = self._temb_cols
         self._temb_w.append(self._w[p + ".time_emb_proj.weight"])
+        self._temb_names.append((p + ".time_emb_proj.weight", off, cout))
         # conv1's bias is folded into the time projection's bias: both are per-channel constants added
         # to conv1's output before norm2 (ResnetBlock2D.forward).
         self._temb_b.append((self._w[p + ".time_emb_proj.bias"].float() + self._w[p + ".conv1.bias"].float()))
@@ -167,10 +191,17 @@ class NetWeights:
             ff1 = self._to_dev(pack_geglu_ln(w[f"{b}.ff.net.0.proj.weight"], w[f"{b}.ff.net.0.proj.bias"], *ln("norm3")))
             blk = BlockW(qkv, self._lin(b + ".attn1.to_out.0"), q2, kv2, self._lin(b + ".attn2.to_out.0"), ff1,
                          self._lin(b + ".ff.net.2"), len(self.transformers))
+            for i, n in enumerate(("to_q", "to_k", "to_v")):
+                self.places[f"{b}.attn1.{n}.weight"] = Place(qkv, c, row0=i * c, fold=ln("norm1"))
+            self.places[f"{b}.attn2.to_q.weight"] = Place(q2, c, fold=ln("norm2"))
+            self.places[f"{b}.attn2.to_k.weight"] = Place(kv2, c, row0=0)
+            self.places[f"{b}.attn2.to_v.weight"] = Place(kv2, c, row0=c)
+            self.places[f"{b}.ff.net.0.proj.weight"] = Place(ff1, ff1.n, geglu=True, fold=ln("norm3"), fold_bias=w[f"{b}.ff.net.0.proj.bias"])
             heads = self.cfg.heads_for(c)
             if c >= self.absorb_min_c and c % heads == 0 and c % 64 == 0 and (c // heads) % 8 == 0:
                 dv = lambda t: self.ops.to_device(t.detach().to(torch.float16).contiguous())  # noqa: E731
                 blk.xa_raw = (dv(w[f"{b}.attn2.to_q.weight"]), dv(ln("norm2")[0]), dv(ln("norm2")[1]))
+                self.places[f"{b}.attn2.to_q.weight"].raw_copy = blk.xa_raw[0]
             self.transformers.append(blk)
             blocks.append(blk)
         # use_linear_projection (SDXL): Linear on the token matrix == the 1x1 conv of SD1.5 in this layout
@@ -180,6 +211,8 @@ class NetWeights:
             # the fused per-token chains (csrc/fused_tail.hip) read these six matrices fragment-major
             for pc in (blocks[0].out1, blocks[0].q2, blocks[0].out2, blocks[0].ff1, blocks[0].ff2, tw.proj_out):
                 pc.weight_frag = self.ops.to_device(add_frag(PackedConv(pc.weight.cpu(), None, pc.n, pc.k, pc.kp, pc.cin, pc.ksize)).weight_frag)
+            for pl in self.places.values():
+                pl.frag = pl.pack.weight_frag is not None
         return tw
 
 

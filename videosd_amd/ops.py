@@ -803,6 +803,25 @@ class HipOps:
         ws = (C.c_float * n)(*[float(w) for w in weights])
         self.ctx.call("vsd_prompt_mix", srcs, ws, n, self._p(dst_buf), self._p(segs_dev), int(nseg), int(frame), self.raw_stream(0))
 
+    # ---- LoRA adapters (include/vsd.h THE ADAPTER FUSE)
+    def lora_fuse_table(self, segs_dev, nseg: int):
+        """have the library check the segment table of `lora_fuse` now (one blocking copy) and remember it by address; segs_dev: the bytes of
+        nseg lib.LoraSeg in device memory (videosd_amd/lora.py AdapterSet).  nseg = 0 forgets it.  The table is kept alive here."""
+        if nseg:
+            self.__dict__.setdefault("_seg_tables", {})[segs_dev.data_ptr()] = segs_dev
+        self.ctx.call("vsd_lora_fuse_table", self._p(segs_dev), int(nseg))
+        if not nseg:
+            self.__dict__.get("_seg_tables", {}).pop(segs_dev.data_ptr(), None)
+
+    def lora_fuse(self, segs_dev, nseg: int, scales):
+        """every segment's fused weight from its base copy and adapters, straight into the packed buffers, ONE launch on this object's own
+        stream (csrc/lora.hip).  scales: up to four floats, launch arguments; the missing ones are 0."""
+        if len(scales) > L.LORA_MAX:
+            raise ValueError(f"lora_fuse: {len(scales)} scales: at most {L.LORA_MAX} adapters")
+        self.__dict__.setdefault("_seg_tables", {})[segs_dev.data_ptr()] = segs_dev
+        sc = (C.c_float * L.LORA_MAX)(*([float(x) for x in scales] + [0.0] * (L.LORA_MAX - len(scales))))
+        self.ctx.call("vsd_lora_fuse", self._p(segs_dev), int(nseg), sc, self.raw_stream(0))
+
     # ---- per-frame options (include/vsd.h: strength and ControlNet scale per frame of one launch)
     def add_noise_frames(self, x0, noise_f32, seeds_dev, kind, draw, coef_dev, coef_stride, hw, batch, out):
         """`add_noise_dev` (noise_f32) or `add_noise_seeded` (seeds_dev, kind, draw) -- exactly one of the two -- with image b reading its two

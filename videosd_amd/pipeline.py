@@ -11,6 +11,7 @@ videosd_amd.engine.Engine (libvsd.so HIP kernels replayed as one hipGraph).
 """
 import gc
 import inspect
+import math
 import os
 import statistics
 import time
@@ -181,6 +182,9 @@ class VideoSDPipeline:
             setattr(self, switch, bool(kwargs.get(switch, False)))
         self.edges, self.canny_thresholds = check_edges(kwargs.get("edges", "sobel"), kwargs.get("canny_thresholds", (100, 200)))
         self.color_match, self._color_a = check_color_match(kwargs.get("color_match"), kwargs.get("color_amount", 1.0))
+        self._loras = self._check_loras(kwargs.get("loras"))  # [(name, path, scale)]: loaded by `load_model`, fused on the device
+        self.lora_skip_text_encoder = bool(kwargs.get("lora_skip_text_encoder", False))
+        self._lora_scales, self.lora_text_encoder_keys_skipped = OrderedDict((n, s) for n, _p, s in self._loras), 0
         self.max_lanes = max(1, int(kwargs.get("lanes", 2)))
         self.tuning_mode = str(kwargs.get("tuning_mode", "auto"))
         self.max_prompts = int(kwargs.get("max_prompts", 8))
@@ -224,6 +228,8 @@ class VideoSDPipeline:
         # `madebyollin/taesd` (:68) unless the extension kwarg `vae=` names another directory.
         mdir = CK.find_snapshot(model_name) or (None if self.is_xl else CK.find_snapshot("SimianLuo/LCM_Dreamshaper_v7"))
         vdir = CK.find_snapshot(self._kwargs.get("vae") or ("madebyollin/taesdxl" if self.is_xl else "madebyollin/taesd"))
+        if self.is_xl and self._loras:
+            raise ValueError("loras=[...] with an SDXL model: adapters are read against the SD1.5 UNet only (SDXL is out of scope)")
         if self.is_xl:
             wu, self.weight_sources["unet"] = load_or_synthesize(W.unet_spec(C.SDXL_UNET), "sdxl.", "unet_sdxl.safetensors", dev, CK.checkpoint_file(mdir, "unet"))
             wv, self.weight_sources["vae"] = load_or_synthesize(W.taesd_spec(C.TAESD), "vae.", "taesdxl.safetensors", dev, CK.checkpoint_file(vdir))
@@ -247,6 +253,7 @@ class VideoSDPipeline:
         wc, self.weight_sources["controlnet"] = load_or_synthesize(W.controlnet_spec(C.SD15_CONTROLNET), "cn.", "controlnet.safetensors", dev, CK.checkpoint_file(cdir))
         wv, self.weight_sources["vae"] = load_or_synthesize(W.taesd_spec(C.TAESD), "vae.", "taesd.safetensors", dev, CK.checkpoint_file(vdir))
         self.model = Engine(ops, C.SD15_UNET, C.SD15_CONTROLNET, C.TAESD, wu, wc, wv)
+        self._load_loras(wu)
         clip_file, tok_dir = _text_files(mdir, "text_encoder", "tokenizer")
         self.weight_sources["text_encoder"] = clip_file or "stand-in embeddings seeded by the prompt text"
         if clip_file is not None:
@@ -369,6 +376,65 @@ class VideoSDPipeline:
 
     color_amount = property(lambda self: self._color_a / COLOR_MAX_AMOUNT, doc="the colour-match amount in [0, 1], as the contract rounds it")
 
+    # ------------------------------------------------------------------ LoRA adapters (include/vsd.h THE ADAPTER FUSE)
+    @staticmethod
+    def _check_loras(loras):
+        """`loras=` of the constructor (also a config.yaml key): up to four {"path": p, "scale": 0.8, "name": "ink"} -> [(name, path, scale)]"""
+        from .lora import MAX_ADAPTERS
+
+        out = []
+        for i, d in enumerate(loras or ()):
+            if not isinstance(d, dict) or "path" not in d or set(d) - {"path", "scale", "name"}:
+                raise ValueError(f'loras[{i}] must be {{"path": ..., "scale": ..., "name": ...}} (scale and name optional), not {d!r}')
+            scale = float(d.get("scale", 1.0))
+            if not math.isfinite(scale):
+                raise ValueError(f"loras[{i}]: scale must be a finite number, not {d.get('scale')!r}")
+            out.append((str(d.get("name") or os.path.splitext(os.path.basename(str(d["path"])))[0]), str(d["path"]), scale))
+        if len(out) > MAX_ADAPTERS:
+            raise ValueError(f"loras: {len(out)} adapters, at most {MAX_ADAPTERS} can be loaded at once")
+        if len({n for n, _p, _s in out}) != len(out):
+            raise ValueError(f"loras: the adapters' names must differ, got {[n for n, _p, _s in out]}")
+        return out
+
+    def _load_loras(self, w_unet):
+        """`load_model`: read the adapter files against the UNet's own tensor names, keep base copies of the tensors they touch, and fuse
+        once at the constructor's scales.  Without `loras` nothing is read, kept or launched."""
+        if not self._loras:
+            return
+        from .lora import load_adapter
+
+        spec = W.unet_spec(self.unet_cfg)
+        ads = [load_adapter(p, spec, skip_text_encoder=self.lora_skip_text_encoder, name=n) for n, p, _s in self._loras]
+        self.lora_text_encoder_keys_skipped = sum(a.text_encoder_keys_skipped for a in ads)
+        self.model.load_adapters(ads, w_unet)
+        self.model.set_adapter_scales(list(self._lora_scales.values()))
+
+    def set_lora_scales(self, scales) -> dict:
+        """{name: scale} for some or all of the loaded adapters: "how much of this style", live.  ONE launch recomputes every adapted
+        weight from its base copy in place (`Engine.set_adapter_scales`): nothing is re-captured, the plan cache survives, cached prompts
+        are rebuilt from their embeddings before their next use.  The weights are shared by every lane, so no launch may be in flight;
+        through a worker the call runs alone, after the launches in flight have been collected."""
+        if not self._lora_scales:
+            raise ValueError("set_lora_scale needs a pipeline built with loras=[...]")
+        new = OrderedDict(self._lora_scales)
+        for name, value in dict(scales).items():
+            if name not in new:
+                raise ValueError(f"no adapter named {name!r}: the loaded adapters are {list(new)}")
+            value = float(value)
+            if not math.isfinite(value):
+                raise ValueError(f"the scale of {name!r} must be a finite number, not {value!r}")
+            new[name] = value
+        self._require_idle("change a LoRA scale")
+        if self.model is not None and new != self._lora_scales:
+            self.model.set_adapter_scales(list(new.values()))
+        self._lora_scales = new
+        return dict(new)
+
+    def set_lora_scale(self, name: str, value: float) -> dict:
+        return self.set_lora_scales({name: value})
+
+    lora_scales = property(lambda self: dict(self._lora_scales), doc="{name: scale} of the loaded adapters")
+
     def option_class(self, options) -> int:
         """What two requests must share to run in ONE launch of a `frame_options` pipeline although their `strength` / `controlnet_scale`
         differ: the NUMBER of timesteps of (strength, steps) -- the program's length (`options`: the kwargs of an `infer` call)."""
@@ -409,6 +475,8 @@ class VideoSDPipeline:
         out["prompts_cached"] = len(self._prompts)
         out["prompt_builds"] = self.prompt_builds
         out["engines_evicted_for_memory"] = self.evictions
+        if self._loras:
+            out["lora_text_encoder_keys_skipped"] = self.lora_text_encoder_keys_skipped
         free, total = torch.cuda.mem_get_info(int(self.device))  # what a leak across plan / prompt changes would show in
         return {"stage_ms_p50": out, "io_bytes_per_frame": dict(self._io_bytes), "device_free_mb": free >> 20, "device_total_mb": total >> 20,
                 "allocated_mb": torch.cuda.memory_allocated(int(self.device)) >> 20}
@@ -851,6 +919,9 @@ class VideoSDPipeline:
         if self.color_match is not None:
             raise ValueError(f'export_plan: this pipeline was built with color_match="{self.color_match}"; its programs call vsd_color_match, which is '
                              'not a plan function: export from a pipeline built with color_match=None (the default)')
+        if self._loras:
+            raise ValueError("export_plan: this pipeline was built with loras=[...]; a plan file would freeze the weights at the scales of the "
+                             "moment and the C library has no entry point that moves them: export from a pipeline built without adapters")
         if isinstance(PM.canonical(options.get("prompt", INFER_DEFAULTS["prompt"])), PM.Mix):
             raise ValueError("export_plan: `prompt` is a mix; a plan file holds ONE cached prompt's constants and the C library forms no mix "
                              "for a plan (vsd_prompt_mix is not a plan function): export with one of the texts")
@@ -865,6 +936,9 @@ class VideoSDPipeline:
         """Another prompt's constants as a file for vsd_plan_load_prompt (a loaded plan takes it without a new plan)."""
         from .plan import export_prompt
 
+        if self._loras:
+            raise ValueError("export_prompt: this pipeline was built with loras=[...]; a prompt's constants depend on the adapted weights and a "
+                             "plan file knows nothing of them: export from a pipeline built without adapters")
         if isinstance(PM.canonical(prompt), PM.Mix):
             raise ValueError("export_prompt: `prompt` is a mix; a prompt file holds ONE cached prompt's constants (it does not say which of its "
                              "bytes are fp16, fp32 or independent of the prompt, so the C side could not mix two of them): export the texts")
