@@ -7,6 +7,7 @@ server.py:104-143), one worker process per GPU, frames sharded round-robin, drop
   python examples/frame_loop.py --factory helpers_fake_pipeline:FakePipeline ...   (any stand-in with the same surface)
   python examples/frame_loop.py --fade-to "a charcoal sketch" --fade-frames 60 ...  (a cross-fade between two prompts, written as 60 mixes)
   python examples/frame_loop.py --color-match histogram:0.8 ...   (every output frame keeps its camera frame's colours, matched on the device)
+  python examples/frame_loop.py --keep-mask banner.png ...   (black in the image: kept as the camera saw it; white: restyled; blended on the device)
 
 Prints one JSON line: frames offered / processed / dropped, output frames per second, p50 / p95 submit->result latency.
 """
@@ -57,10 +58,15 @@ async def run(args):
     if args.color_match:  # MODE[:AMOUNT] -> the constructor's color_match / color_amount (fixed mode; `set_color_match` moves the amount live)
         mode, _, amount = args.color_match.partition(":")
         extra.update(color_match=mode, color_amount=float(amount) if amount else 1.0)
+    if args.keep_mask:  # FILE -> the constructor's keep_mask=True; the image itself goes to every worker below (`set_mask`, any size)
+        extra.update(keep_mask=True)
     workers = [RemotePipeline(factory=args.factory, batch=args.batch, device=i, **cfg, **extra) for i in range(args.gpus)]
     opts = dict(prompt=args.prompt, height=args.height, width=args.width, strength=args.strength, steps=args.steps,
                 controlnet_scale=args.controlnet_scale, seed=23)
     try:
+        if args.keep_mask:  # drawn over the camera picture: each worker sizes it once per frame size, as it sizes the frames
+            mask = Image.open(args.keep_mask).convert("L")
+            await asyncio.gather(*[w.set_mask.remote(mask) for w in workers])
         if not args.no_warmup:  # the first call of a worker builds and captures its graph (compile_model in the reference)
             await asyncio.gather(*[w.infer.remote(camera_frame(0, 640, 480), **opts) for w in workers])
         disp = FrameDispatcher(workers, mode=args.mode, depth=args.depth or args.batch * 2)
@@ -125,6 +131,8 @@ def main(argv=None):
                     help="a LoRA adapter file (safetensors) fused on the device at SCALE (default 1.0); up to four")
     ap.add_argument("--color-match", dest="color_match", default="", metavar="MODE[:AMOUNT]",
                     help="histogram or meanstd, and an amount in [0, 1] (default 1): transfer each camera frame's colours onto its output frame")
+    ap.add_argument("--keep-mask", dest="keep_mask", default="", metavar="FILE",
+                    help="an image of any size, read as gray: 0 / black is kept as the camera saw it, 255 / white is restyled, values between blend")
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--strength", type=float, default=0.6)

@@ -623,6 +623,53 @@ int vsd_color_match(vsd_ctx* ctx, const void* src_u8, void* dst_u8, int frames, 
                     void* stream);
 int vsd_color_match_host(const void* src_u8, void* dst_u8, int h, int w, int mode, int amount);
 
+/* ---- Keep masks: restyle part of each frame, anchored in latent space (csrc/keep_mask.hip, csrc/keep_mask_core.h; the latent anchor ----
+ * beside the scheduler bodies in csrc/noise.hip).  "Restyle this part, leave that part as the camera saw it": a banner or UI strip of a
+ * fixed installation, a subject segmented on the client, a picture-in-picture region.  Two stages inside the recorded program make that
+ * more than a paste-over: the usual masked img2img rule at every denoising step (in the kept region the next sample is the INPUT's
+ * latents noised to the next timestep, so the UNet sees the real surroundings and paints up to them), and a pixel blend behind
+ * vsd_postprocess_rgb.  The reference has no such stage; here it is opt-in and the default program does not change.
+ * THE KEEP MASK (fixed; device kernels, the host twins and the tests are held to it to the bit):
+ *   inputs        the mask: u8 [h][w], one per frame of a launch, in device memory.  255 = fully restyled (the program's output), 0 = kept
+ *                 (the camera's pixel).  The integer weight of a mask byte m is a = m + (m >> 7): 0..256, and 256 exactly at m = 255.
+ *   pixel stage   out[p][c] = (in[p][c]*(256 - a) + out[p][c]*a + 128) >> 8, a of pixel p: at a = 256 the output byte is unchanged, at
+ *                 a = 0 it is the input byte.  in and out: packed u8 [h][w][3]; out is rewritten in place.  Any h, w >= 1 (sides up to
+ *                 VSD_RESAMPLE_MAX_SIDE) and any byte alignment of all three pointers.
+ *   latent weight h and w multiples of 8 (anything else is refused).  For latent pixel (y, x) of the h/8 x w/8 grid, S = the sum of a over
+ *                 its 8 x 8 block, 0..16384, and wl = (float)S / 16384.0f: wl and 1 - wl are exact in fp32.
+ *   latent anchor per channel 0..3 of a latent row of 8 halves (channels 4..7 stay as they are); fp32, nothing contracted, an fma only
+ *                 where written; every fma's result exists in fp32 before it is rounded to fp16.
+ *     after every step (it matters after every step but the last: nothing reads the last step's sample):
+ *                 kept = fma(sap, (float)x0[c], sbp * n0[c]), where sap, sbp are coefficients 4 and 5 of that step's six (the next
+ *                 timestep's, the ones lcm_step reads) and n0 is draw 0 of kind 0 -- the draw add_noise used for this frame: the kept
+ *                 region is the frame's own initial noising carried to the next timestep, as masked img2img pipelines do.
+ *                 lat[c] = (wl == 1) ? lat[c] unchanged : fp16(fma(wl, (float)lat[c], (1 - wl) * kept))
+ *     after the last step:
+ *                 den[c] = (wl == 1) ? den[c] : fp16(fma(wl, (float)den[c], (1 - wl) * (float)x0[c]))
+ *                 dec_in[c] = fp16(tanhf((float)den[c] / 3.0f) * 3.0f), the expression of the scheduler step (channels 4..7: zero)
+ *     The pass-through at wl == 1 makes an all-255 mask reproduce the default program's bits, signed zeros included.
+ * vsd_mask_blend: `frames` frames per call, frame f at src_u8 / dst_u8 + f*3*N and mask_u8 + f*N; one launch on `stream`; 16 pixels per
+ *   lane and step as 16-byte words where the three pointers allow it, single pixels elsewhere.  No LDS, no atomics, no workspace.
+ * vsd_mask_latent: one launch; writes weights_f32 [frames][h/8 * w/8] (4-byte aligned).
+ * vsd_latent_keep: one launch, one thread per latent pixel, blockIdx.y = image, in place.  weights_f32: [batch][hw], what vsd_mask_latent
+ *   wrote.  coef_stride counts floats between two images' six coefficients at coef_dev; 0: all images share them (the _dev layout).
+ *   Step form: exactly one of noise_f32 (fp32 [4][hw], draw 0) / seeds_dev (with kind, draw: the NOISE CONTRACT's) is given, `lat` is
+ *   given, `den` and `dec_in` are NULL.  Final form: neither noise source, `lat` NULL, `den` and `dec_in` given, coef_dev may be NULL.
+ *   Every other combination is refused with a message.
+ * vsd_mask_blend_host / vsd_mask_latent_host / vsd_latent_keep_host: the same arithmetic as plain host loops over HOST memory; no GPU,
+ *   no context (VSD_ERR_ARG without a message).  vsd_latent_keep_host takes table noise only and `coef` in host memory, and writes `lat`
+ *   (step form) or `den` (final form) only: the host's tanhf is not the device's, so it writes no dec_in.
+ * None of these is a plan function: a program that records them has no plan-file export. */
+#define VSD_MASK_MAX_FRAMES 1024
+int vsd_mask_blend(vsd_ctx* ctx, const void* src_u8, void* dst_u8, const void* mask_u8, int frames, int h, int w, void* stream);
+int vsd_mask_latent(vsd_ctx* ctx, const void* mask_u8, int frames, int h, int w, void* weights_f32, void* stream);
+int vsd_latent_keep(vsd_ctx* ctx, const void* x0, const void* weights_f32, const void* noise_f32, const void* seeds_dev, int kind, int draw,
+                    const void* coef_dev, int coef_stride, int hw, int batch, void* lat, void* den, void* dec_in, void* stream);
+int vsd_mask_blend_host(const void* src_u8, void* dst_u8, const void* mask_u8, int frames, int h, int w);
+int vsd_mask_latent_host(const void* mask_u8, int frames, int h, int w, float* weights_f32);
+int vsd_latent_keep_host(const void* x0, const float* weights_f32, const float* noise_f32, const float* coef, int coef_stride, int hw, int batch,
+                         void* lat, void* den);
+
 /* ---- two independent operations as ONE grid per kernel ------------------------------------------------
  * The reference runs the ControlNet and then the UNet encoder of a denoising step -- the same topology with two weight sets on the
  * same latents (lcm_controlnet.py:539-577) -- as two sequences of cuDNN / cuBLAS launches.  Here the two walk in lock step:

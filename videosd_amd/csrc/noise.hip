@@ -279,3 +279,126 @@ extern "C" int vsd_lcm_step_frames(vsd_ctx* ctx, const void* eps, const void* sa
     launch_lcm_step(s, eps, sample, noise_f32 != nullptr, TableNoise{(const float*)noise_f32}, k, hw, batch, prev, denoised, dec_in);
   return ls.finish();
 }
+
+// ---- the latent anchor of a keep mask (include/vsd.h THE KEEP MASK): beside the bodies above because it reads their noise and coefficient
+// sources.  Per channel 0..3 in fp32 (channels 4..7 stay as they are); blockIdx.y = image of the launch; a row whose weight is 1 is not written:
+//   step:  kept = fma(sap, x0, sbp * n0);  lat = fp16(fma(wl, lat, (1 - wl) * kept))
+//   final: den = fp16(fma(wl, den, (1 - wl) * x0));  dec_in = fp16(tanhf(den / 3) * 3), lcm_step_kernel's expression, for every row
+namespace {
+
+__device__ __host__ __forceinline__ float keep_blend(float wl, float mine, float kept) { return __builtin_fmaf(wl, mine, (1.0f - wl) * kept); }
+__device__ __host__ __forceinline__ float keep_noised(float sap, float x, float sbp, float n) { return __builtin_fmaf(sap, x, sbp * n); }
+
+template <class Noise, class Coef>
+__global__ void latent_keep_step_kernel(const half_t* __restrict__ x0, const float* __restrict__ weights, Noise noise, Coef coef, int hw,
+                                        half_t* __restrict__ lat) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= hw) return;
+  const size_t row = (size_t)blockIdx.y * hw + i;
+  const float wl = weights[row];
+  if (wl == 1.0f) return;
+  const auto& k = coef_of(coef, blockIdx.y);
+  const float sap = k[4], sbp = k[5];
+  const Normal4 nz = noise(hw, blockIdx.y, (uint32_t)i);
+  half8 x = *reinterpret_cast<const half8*>(x0 + row * 8);
+  half8 l = *reinterpret_cast<const half8*>(lat + row * 8);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float v = keep_blend(wl, (float)l[c], keep_noised(sap, (float)x[c], sbp, nz.z[c]));
+    asm volatile("" : "+v"(v));  // v exists in fp32 before it is rounded to fp16: no v_fma_mixlo_f16 (emits nothing)
+    l[c] = (half_t)v;
+  }
+  *reinterpret_cast<half8*>(lat + row * 8) = l;
+}
+
+__global__ void latent_keep_final_kernel(const half_t* __restrict__ x0, const float* __restrict__ weights, int hw, half_t* __restrict__ den,
+                                         half_t* __restrict__ dec_in) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= hw) return;
+  const size_t row = (size_t)blockIdx.y * hw + i;
+  const float wl = weights[row];
+  half8 d = *reinterpret_cast<const half8*>(den + row * 8);
+  half8 oi = (half8){0, 0, 0, 0, 0, 0, 0, 0};
+  if (wl != 1.0f) {
+    half8 x = *reinterpret_cast<const half8*>(x0 + row * 8);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float v = keep_blend(wl, (float)d[c], (float)x[c]);
+      asm volatile("" : "+v"(v));
+      d[c] = (half_t)v;
+    }
+    *reinterpret_cast<half8*>(den + row * 8) = d;
+  }
+#pragma unroll
+  for (int c = 0; c < 4; ++c) oi[c] = (half_t)(tanhf((float)d[c] / 3.0f) * 3.0f);
+  *reinterpret_cast<half8*>(dec_in + row * 8) = oi;
+}
+
+template <class Noise, class Coef>
+void launch_latent_keep(hipStream_t s, const void* x0, const void* weights, Noise noise, Coef k, int hw, int batch, void* lat) {
+  hipLaunchKernelGGL((latent_keep_step_kernel<Noise, Coef>), dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)x0, (const float*)weights, noise,
+                     k, hw, (half_t*)lat);
+}
+
+template <class Noise>
+void launch_latent_keep(hipStream_t s, const void* x0, const void* weights, Noise noise, const void* coef_dev, int coef_stride, int hw, int batch,
+                        void* lat) {
+  if (coef_stride)
+    launch_latent_keep(s, x0, weights, noise, FrameCoef{(const float*)coef_dev, coef_stride}, hw, batch, lat);
+  else
+    launch_latent_keep(s, x0, weights, noise, (const float*)coef_dev, hw, batch, lat);
+}
+
+}  // namespace
+
+extern "C" int vsd_latent_keep(vsd_ctx* ctx, const void* x0, const void* weights_f32, const void* noise_f32, const void* seeds_dev, int kind, int draw,
+                               const void* coef_dev, int coef_stride, int hw, int batch, void* lat, void* den, void* dec_in, void* stream) {
+  if (!ctx) return VSD_ERR_ARG;
+  if (!x0 || !weights_f32 || hw <= 0 || batch < 1 || batch > 65535 || ((uintptr_t)weights_f32 & 3))
+    return vsd_fail(ctx, VSD_ERR_ARG, "latent_keep: bad arguments (x0, weights_f32 4-byte aligned, hw >= 1, batch 1..65535)");
+  hipStream_t s = (hipStream_t)stream;
+  if (lat) {  // the step form
+    if (den || dec_in) return vsd_fail(ctx, VSD_ERR_ARG, "latent_keep: the step form (lat given) takes neither den nor dec_in");
+    if ((noise_f32 != nullptr) == (seeds_dev != nullptr))
+      return vsd_fail(ctx, VSD_ERR_ARG, "latent_keep: the step form needs exactly one of noise_f32 and seeds_dev");
+    if (!coef_dev || ((uintptr_t)coef_dev & 3) || (coef_stride != 0 && coef_stride < 6))
+      return vsd_fail(ctx, VSD_ERR_ARG, "latent_keep: the step form needs coef_dev (4-byte aligned) and coef_stride 0 or >= 6, got %d", coef_stride);
+    if (seeds_dev && (kind < 0 || draw < 0)) return vsd_fail(ctx, VSD_ERR_ARG, "latent_keep: kind=%d draw=%d", kind, draw);
+    LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+    if (noise_f32)
+      launch_latent_keep(s, x0, weights_f32, TableNoise{(const float*)noise_f32}, coef_dev, coef_stride, hw, batch, lat);
+    else
+      launch_latent_keep(s, x0, weights_f32, SeededNoise{(const uint32_t*)seeds_dev, (uint32_t)kind, (uint32_t)draw}, coef_dev, coef_stride, hw, batch, lat);
+    return ls.finish();
+  }
+  if (!den || !dec_in) return vsd_fail(ctx, VSD_ERR_ARG, "latent_keep: give lat (the step form) or den and dec_in (the final form)");
+  if (noise_f32 || seeds_dev) return vsd_fail(ctx, VSD_ERR_ARG, "latent_keep: the final form (den, dec_in) takes no noise source");
+  LaunchScope ls(ctx, s, VSD_FAM_ELEMENTWISE, 0.0);
+  hipLaunchKernelGGL(latent_keep_final_kernel, dim3(cdiv(hw, 256), batch), dim3(256), 0, s, (const half_t*)x0, (const float*)weights_f32, hw, (half_t*)den,
+                     (half_t*)dec_in);
+  return ls.finish();
+}
+
+// The anchor as plain host loops over HOST memory (no context): table noise only, writes lat (step form) or den (final form) only --
+// the host's tanhf is not the device's, so there is no dec_in here.  coef: image b reads sap, sbp at coef[b * coef_stride + 4], [.. + 5].
+extern "C" int vsd_latent_keep_host(const void* x0, const float* weights_f32, const float* noise_f32, const float* coef, int coef_stride, int hw,
+                                    int batch, void* lat, void* den) {
+  if (!x0 || !weights_f32 || hw <= 0 || batch < 1 || batch > 65535) return VSD_ERR_ARG;
+  const bool step = lat != nullptr;
+  if (step ? (den || !noise_f32 || !coef || (coef_stride != 0 && coef_stride < 6)) : (!den || noise_f32)) return VSD_ERR_ARG;
+  const half_t* x = (const half_t*)x0;
+  half_t* out = (half_t*)(step ? lat : den);
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < hw; ++i) {
+      const size_t row = (size_t)b * hw + i;
+      const float wl = weights_f32[row];
+      if (wl == 1.0f) continue;
+      for (int c = 0; c < 4; ++c) {
+        const float xc = (float)x[row * 8 + c];
+        const float kept = step ? keep_noised(coef[(size_t)b * coef_stride + 4], xc, coef[(size_t)b * coef_stride + 5], noise_f32[(size_t)c * hw + i]) : xc;
+        const volatile float v = keep_blend(wl, (float)out[row * 8 + c], kept);  // (rounded to fp32 first, as on the device)
+        out[row * 8 + c] = (half_t)v;
+      }
+    }
+  return VSD_OK;
+}

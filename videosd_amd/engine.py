@@ -37,6 +37,8 @@ from .ops import Geom
 from .packing import _round_up as _ru
 from .program import SYNC_OPS, Arena, Recorder, capture, flat_calls, launches_by_kind
 
+KEEP_MASK_OPS = ("mask_latent", "latent_keep", "mask_blend")  # what `prepare(keep_mask=True)` records besides the default program's ops
+
 
 def _env_switch(name: str, default: bool) -> bool:
     """an A/B switch of the environment: unset -> `default`, "1" -> on, anything else -> off"""
@@ -75,6 +77,15 @@ class SchedulerOps:
             r.lcm_step_seeded(eps, cur, seeds, 0, draw, coef, hw, batch, nxt, den, dec_in)
         else:
             r.lcm_step_dev(eps, cur, table, coef, hw, batch, nxt, den, dec_in)
+
+    def latent_keep(self, r, x0, weights, coef, batch, lat):
+        """the step form of the keep mask's latent anchor behind an `lcm_step`: that step's coefficients, this plan's coefficient form and
+        draw 0 of kind 0 from this plan's noise source (what `add_noise` gave the frame)"""
+        seeds = self.seeds
+        r.latent_keep(x0, weights, None if seeds is not None else self.noise[0], seeds, 0, 0, coef, self.coef_stride, self.hw, batch, lat, None, None)
+
+    def latent_keep_final(self, r, x0, weights, batch, den, dec_in):
+        r.latent_keep(x0, weights, None, None, 0, 0, None, 0, self.hw, batch, None, den, dec_in)
 
 
 class RefCtx:
@@ -191,6 +202,14 @@ class Engine:
         self._color_host = None      # ... their pinned mirror
         self.color_a = None          # ... what the next launch runs with: a tuple of B integers (`set_color_amount`)
         self._color_sent = None      # ... and what `color_amounts` holds (`_sync_color`)
+        self.keep_mask = False       # the keep-mask stages (include/vsd.h THE KEEP MASK) are part of the program
+        self.mask_u8 = None          # ... the masks on the device, u8 [B][H][W] (255: restyled, 0: kept): the program reads them when it runs
+        self.mask_w = None           # ... their latent weights, fp32 [B][hw0], written by the program's `mask_latent`
+        self._mask_host = None       # ... the masks' pinned mirror
+        self._mask_want = None       # ... what the next launch runs with: u8 [B][H][W] on the host (`set_masks`)
+        self._mask_epoch = 0         # ... counts the `set_masks` calls that changed `_mask_want`
+        self._mask_sent = None       # ... and the epoch `mask_u8` holds (`_sync_mask`)
+        self._mask_pipe_epoch = None  # ... and which mask of the pipeline `_mask_want` is (VideoSDPipeline sets it; None: a launch's own masks)
         self.ref_u8 = None           # `ref_mode`: the reference image
         self._ref_epoch = None       # ... and which reference image of the pipeline `ref_u8` holds (VideoSDPipeline sets it)
         self.noise = None            # the host draws on the device (None: `device_seed`)
@@ -1094,7 +1113,8 @@ class Engine:
     def prepare(self, H: int, W: int, steps: int, strength: float, controlnet_scale: float = 1.0,
                 use_controlnet: bool = True, use_graph: Optional[bool] = None, autotune: bool = True, batch: int = 1,
                 ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False, frame_options: bool = False,
-                edges: str = "sobel", canny_thresholds=(100, 200), color_match: Optional[str] = None, color_amount=1.0):
+                edges: str = "sobel", canny_thresholds=(100, 200), color_match: Optional[str] = None, color_amount=1.0,
+                keep_mask: bool = False):
         """Fix the frame geometry and schedule; build the static program and capture it into a hipGraph
         (the reference's intent at videopipeline.py:35-47, `compile_model`).
 
@@ -1138,7 +1158,16 @@ class Engine:
         all B frames right behind `postprocess_rgb`, from `frame_u8` onto `out_u8` in place.  color_amount: a number in [0, 1] (0: the
         output as it is, 1: fully matched), the value every frame starts with; `set_color_amount` changes it per frame from the next launch on
         without a re-capture.  Composes with every other mode (the source is whatever ended up in `frame_u8`; ref_mode and SDXL
-        included).  Such a program has no plan-file export (`vsd_color_match` is not a plan function)."""
+        included).  Such a program has no plan-file export (`vsd_color_match` is not a plan function).
+
+        keep_mask: every frame of the launch has a u8 [H][W] mask (`set_masks`; 255: restyled, 0: kept as the camera saw it; all 255 until
+        then) by THE KEEP MASK of include/vsd.h.  The program records `mask_latent` once ahead of the first step, a `latent_keep` right
+        behind every `lcm_step` (in the kept region the next sample is the input's latents noised to the next timestep with the frame's own
+        draw 0, so the UNet sees the real surroundings at every step) and one more, the final form, behind the last (the denoised latents
+        give way to the input's), and `mask_blend(frame_u8 -> out_u8)` behind `postprocess_rgb` -- behind `color_match` when both are
+        on: colours are matched over the whole frame first.  With all-255 masks the frames are the default program's bit for bit.  New
+        masks are one B*H*W-byte copy ahead of the next launch (`_sync_mask`), no re-capture; a slot has masks of its own.  Composes with
+        device_seed, frame_prompts, frame_options, edges and color_match; not with ref_mode or an SDXL UNet.  No plan-file export."""
         edges, canny_thresholds = L.check_edges(edges, canny_thresholds)
         if edges == "canny" and not hasattr(self.ops, "canny_control"):
             raise ValueError('edges="canny" needs the op canny_control, which this ops object does not have')
@@ -1147,6 +1176,12 @@ class Engine:
             raise ValueError(f'color_match="{color_match}" needs the op color_match, which this ops object does not have')
         if color_match is not None and H * W > L.COLOR_MAX_PIXELS:
             raise ValueError(f'color_match="{color_match}": a {W} x {H} frame has more than {L.COLOR_MAX_PIXELS} pixels (include/vsd.h VSD_COLOR_MAX_PIXELS)')
+        if keep_mask:
+            missing = [f for f in KEEP_MASK_OPS if not hasattr(self.ops, f)]
+            if missing:
+                raise ValueError(f"keep_mask=True needs the op(s) {', '.join(missing)}, which this ops object does not have")
+            if ref_mode or self.unet.add_l1 is not None:
+                raise ValueError("keep_mask=True: reference-only (ref_mode) and SDXL programs have no keep-mask stages")
         self._check_arguments(H, W, batch, use_controlnet, ref_mode, device_seed, frame_prompts, frame_options)
         sched = LCMSchedule(strength, steps)
         self._prepare_prompt_block(batch, frame_prompts)
@@ -1161,6 +1196,12 @@ class Engine:
             self.color_amounts = self.ops.zeros(batch, dtype=torch.int32)
             self._color_host = torch.zeros(batch, dtype=torch.int32, pin_memory=torch.cuda.is_available())
             self.set_color_amount(color_a / L.COLOR_MAX_AMOUNT)
+        self.keep_mask = bool(keep_mask)
+        if keep_mask:  # (this engine's own as well)
+            self.mask_u8 = self.ops.zeros(batch, H, W, dtype=torch.uint8)
+            self.mask_w = self.ops.zeros(batch, (H // 8) * (W // 8), dtype=torch.float32)
+            self._mask_host = torch.zeros(batch, H, W, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+            self.set_masks(None)
         # The lock-step encoders are the one-stream form of EVERY program.  What a pair's grid looks like depends on the mode: a one-frame
         # program (latency mode) takes the pair's own table entry, timed alone; a coalesced launch on busy lanes (throughput mode) runs
         # the pair in the form its members have as launches of their own -- a latency-chosen form there occupies more workgroup-time
@@ -1177,7 +1218,7 @@ class Engine:
         self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=len(sched), batch=batch,
                          ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), frame_options=bool(frame_options), tuned_for_lanes=bool(self.tune_for_lanes),
                          edge_mode=self.edges, canny_thresholds=self.canny_thresholds,  # ("edges" is taken: the event edges of the captured sequence)
-                         color_match=self.color_mode,
+                         color_match=self.color_mode, keep_mask=self.keep_mask,
                          sizes=self._level_sizes(H, W), timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=self.arena.peak)
         self._warm_up_and_capture(autotune)
         return self.plan
@@ -1339,6 +1380,8 @@ class Engine:
             self.buffers["ref_x0"] = ref_x0
         # every frame gets the same draws: the reference resets its RNG per frame
         sops.add_noise(r, x0, 0, 0, c[0:2], B, lat[0])
+        if self.keep_mask:  # the latent weights of this launch's masks, ahead of the first step
+            r.mask_latent(self.mask_u8, B, H, W, self.mask_w)
         mark = a.mark()
         for i in range(n):
             a.rewind(mark)
@@ -1387,10 +1430,16 @@ class Engine:
             last = i == n - 1
             # (draw i + 1; 0: a one-step schedule adds none)
             sops.lcm_step(r, eps, cur, i + 1 if sched.multistep else 0, c[2 + 6 * i:8 + 6 * i], B, nxt, den, dec_in if last else None)
+            if self.keep_mask:  # the kept region of the next sample: x0 noised to the next timestep (the step's own coefficients 4, 5)
+                sops.latent_keep(r, x0, self.mask_w, c[2 + 6 * i:8 + 6 * i], B, nxt)
+                if last:
+                    sops.latent_keep_final(r, x0, self.mask_w, B, den, dec_in)
         self._decode(r, dec_in, h0, w0, dec_out)
         r.postprocess_rgb(dec_out, 8, B * H * W, out_b)
         if self.color_mode is not None:  # ahead of everything that reads `out_u8` (`collect_u8`, the queued `rgb_to_i420`)
             r.color_match(frame_b, out_b, B, H, W, self.color_mode, self.color_amounts)
+        if self.keep_mask:  # (likewise ahead of every reader; the colours were matched over the whole frame first)
+            r.mask_blend(frame_b, out_b, self.mask_u8, B, H, W)
         # program: what a lone launch runs (the ControlNet encoder on the side stream when `overlap_controlnet`);
         # program_serial: everything on the lane's own stream (the encoders in lock step when `twin_encoders`)
         self.program = r.flavor(0 if self.overlap_controlnet or not self._twin_now else 1)
@@ -1403,6 +1452,7 @@ class Engine:
         self._sync_prompt()
         self._sync_options()
         self._sync_color()
+        self._sync_mask()
         if autotune:  # (only shapes missing from the shared table are timed: a slot with the parent's batch size finds all)
             self.autotune()
         self.program.run()
@@ -1495,6 +1545,45 @@ class Engine:
             self.ops.upload(self.color_amounts, self._color_host)
             self._color_sent = self.color_a
 
+    def set_masks(self, masks):
+        """The keep masks of the launches from the next one on: one u8 [H][W] array for every frame, B of them ([B][H][W] or a sequence),
+        or None for all 255 (everything restyled).  Only noted here (a launch in flight keeps the masks it was submitted with); `launch`
+        sends changed masks ahead of the program (`_sync_mask`): no re-capture, no drain."""
+        if self.mask_u8 is None:
+            raise ValueError("set_masks needs an engine prepared with keep_mask=True")
+        B, H, W = self.mask_u8.shape
+        if masks is None:
+            want = np.full((B, H, W), 255, dtype=np.uint8)
+        else:
+            if isinstance(masks, (list, tuple)):
+                if len(masks) != B:
+                    raise ValueError(f"masks must be one [H][W] array or {B} of them (one per frame of the launch), not {len(masks)}")
+                masks = [np.asarray(m) for m in masks]
+                if any(m.shape != (H, W) for m in masks):
+                    raise ValueError(f"every mask must be a u8 array of shape ({H}, {W}), not {[m.shape for m in masks]}")
+                if any(m.dtype != np.uint8 for m in masks):
+                    raise ValueError("every mask must be a u8 array")
+                masks = np.stack(masks)
+            m = np.asarray(masks)
+            if m.dtype != np.uint8:
+                raise ValueError(f"masks must be u8 (255: restyled, 0: kept), not {m.dtype}")
+            if m.shape == (H, W):
+                m = np.broadcast_to(m, (B, H, W))
+            elif m.shape != (B, H, W):
+                raise ValueError(f"masks must have shape ({H}, {W}) or ({B}, {H}, {W}), not {m.shape}")
+            want = np.array(m, dtype=np.uint8, order="C")  # (a copy: the caller may draw on in its array)
+        if self._mask_want is None or not np.array_equal(want, self._mask_want):
+            self._mask_want = want
+            self._mask_epoch += 1
+
+    def _sync_mask(self):
+        """the masks of `set_masks` on the lane's stream ahead of the program, when they changed: B*H*W bytes from the pinned mirror (the
+        lane's previous launch has been collected, so nothing in flight reads the mirror)"""
+        if self.mask_u8 is not None and self._mask_sent != self._mask_epoch:
+            self._mask_host.numpy()[:] = self._mask_want
+            self.ops.upload(self.mask_u8, self._mask_host)
+            self._mask_sent = self._mask_epoch
+
     @staticmethod
     def host_noise(n_steps: int, h: int, w: int, ref: bool = False):
         """The CPU draws of one frame, in the reference's order: draw 0 = prepare_latents noise
@@ -1530,6 +1619,7 @@ class Engine:
         self._sync_prompt()
         self._sync_options()
         self._sync_color()
+        self._sync_mask()
         if self.graph is not None:
             ov = self.overlap_launch if overlap is None else overlap
             self.ops.seq_launch(self.graph if ov else self.graph_serial)

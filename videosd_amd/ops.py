@@ -745,6 +745,22 @@ class HipOps:
         self.ctx.call("vsd_color_match", self._p(src_u8), self._p(dst_u8), int(frames), int(h), int(w), int(L.COLOR_MODES[mode]),
                       self._p(amounts_dev), self._p(ws), self.s)
 
+    def mask_blend(self, src_u8, dst_u8, mask_u8, frames, h, w):
+        """`src_u8` blended into `dst_u8` in place by THE KEEP MASK of include/vsd.h (csrc/keep_mask.hip): `frames` packed [h][w][3] frames
+        each, one u8 [h][w] mask per frame (255: dst stays, 0: the src pixel).  One launch, no workspace."""
+        self.ctx.call("vsd_mask_blend", self._p(src_u8), self._p(dst_u8), self._p(mask_u8), int(frames), int(h), int(w), self.s)
+
+    def mask_latent(self, mask_u8, frames, h, w, weights_f32):
+        """the masks' latent weights: fp32 [frames][h/8 * w/8], the mean of the integer weight over every 8 x 8 block (one launch)"""
+        self.ctx.call("vsd_mask_latent", self._p(mask_u8), int(frames), int(h), int(w), self._p(weights_f32), self.s)
+
+    def latent_keep(self, x0, weights_f32, noise_f32, seeds_dev, kind, draw, coef_dev, coef_stride, hw, batch, lat=None, den=None, dec_in=None):
+        """The latent anchor of a keep mask, in place.  Step form (`lat`; exactly one of noise_f32 / seeds_dev): where the weight is below 1,
+        `lat` moves towards x0 noised to the next timestep with draw 0 (coefficients 4, 5 of the six at coef_dev; image b's at
+        + b * coef_stride floats, 0: shared).  Final form (`den`, `dec_in`; no noise source): `den` moves towards x0, `dec_in` follows."""
+        self.ctx.call("vsd_latent_keep", self._p(x0), self._p(weights_f32), self._p(noise_f32), self._p(seeds_dev), int(kind), int(draw),
+                      self._p(coef_dev), int(coef_stride), int(hw), int(batch), self._p(lat), self._p(den), self._p(dec_in), self.s)
+
     def add_noise(self, x0, noise_f32, sqrt_a, sqrt_b, hw, out):
         self.ctx.call("vsd_add_noise", self._p(x0), self._p(noise_f32), sqrt_a, sqrt_b, hw, self._p(out), self.s)
 

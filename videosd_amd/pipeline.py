@@ -165,6 +165,14 @@ class VideoSDPipeline:
             frame-to-frame colour flicker of a few-step LCM.  Default None: no such stage, the same programs and bits as before.  The mode
             is fixed for the life of the object; `set_color_match(amount)` changes the amount live (no re-capture; a worker collects its launches in flight first).  Composes with every
             switch above, with I420 frames, reference-only mode and SDXL; such a pipeline has no `export_plan`.
+        keep_mask=True: part of every frame is kept as the camera saw it, by THE KEEP MASK of include/vsd.h: `set_mask(mask)` (255 / white:
+            restyled, 0 / black: kept, values between blend; everything restyled until then) holds for every launch submitted from then
+            on, `infer_batch(imgs, masks=[...])` takes one mask per frame.  Inside the captured program the kept region of the latents is
+            the input's own, noised to the step's timestep, at every denoising step -- the model sees what surrounds the part it paints --
+            and the camera's pixels are blended over the output behind the decoder, so PIL, numpy and I420 callers all get the blended
+            frame.  Default False: no such stages, the same programs and bits as before.  Fixed for the life of the object; a new mask is
+            one copy ahead of the next launch, no re-capture.  Composes with every switch above and with I420 frames; not with SDXL or
+            reference-only frames (refused by name); such a pipeline has no `export_plan` / `export_prompt`.
         lanes: launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on launch
             stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch.
         tuning_mode: "auto": shapes missing from the table are timed on this GPU at `prepare`; "table": never -- they take the deterministic
@@ -182,6 +190,8 @@ class VideoSDPipeline:
             setattr(self, switch, bool(kwargs.get(switch, False)))
         self.edges, self.canny_thresholds = check_edges(kwargs.get("edges", "sobel"), kwargs.get("canny_thresholds", (100, 200)))
         self.color_match, self._color_a = check_color_match(kwargs.get("color_match"), kwargs.get("color_amount", 1.0))
+        self.keep_mask = bool(kwargs.get("keep_mask", False))
+        self._mask_img, self._mask_epoch, self._mask_sized = None, 0, {}  # `set_mask`: the mask as an "L" image, its count, (width, height) -> u8 [h][w]
         self._loras = self._check_loras(kwargs.get("loras"))  # [(name, path, scale)]: loaded by `load_model`, fused on the device
         self.lora_skip_text_encoder = bool(kwargs.get("lora_skip_text_encoder", False))
         self._lora_scales, self.lora_text_encoder_keys_skipped = OrderedDict((n, s) for n, _p, s in self._loras), 0
@@ -374,6 +384,65 @@ class VideoSDPipeline:
         self._color_a = check_color_amount(amount)
         return self.color_amount
 
+    @staticmethod
+    def _mask_image(mask) -> Image.Image:
+        """a mask as callers give it -- a PIL "L" / "1" image or a 2-D u8 array, of any size -- as an "L" image"""
+        if isinstance(mask, Image.Image):
+            if mask.mode not in ("L", "1"):
+                raise ValueError(f'a mask image must have mode "L" or "1" (255 / white: restyled, 0 / black: kept), not "{mask.mode}"')
+            img = mask.convert("L")
+        else:
+            m = np.asarray(mask)
+            if m.ndim != 2 or m.dtype != np.uint8:
+                raise ValueError(f"a mask must be a PIL L / 1 image or a 2-D u8 array, not {type(mask).__name__} of shape {getattr(m, 'shape', None)}, {getattr(m, 'dtype', None)}")
+            img = Image.fromarray(np.ascontiguousarray(m), mode="L")
+        if min(img.size) < 1:
+            raise ValueError("a mask must have at least one pixel")
+        return img
+
+    @staticmethod
+    def _size_mask(img: Image.Image, width: int, height: int) -> np.ndarray:
+        """the mask at the size of a launch's frames, by the rule that sizes a frame (`_launch_frames`): the centre crop + LANCZOS resize of
+        `center_crop_resize`, then, for a size that is not a multiple of 8, the second LANCZOS step down to one -- so a mask drawn over the
+        camera picture lines up with the camera's frames"""
+        out = center_crop_resize(img, width, height)
+        if height % 8 or width % 8:
+            out = out.resize((width - width % 8, height - height % 8), resample=Image.Resampling.LANCZOS)
+        return np.array(out, dtype=np.uint8)
+
+    def set_mask(self, mask) -> int:
+        """The keep mask of every launch submitted from now on (`keep_mask=True` of the constructor): a PIL "L" / "1" image or a 2-D u8 array
+        of ANY size -- 255 / white: restyled, 0 / black: kept as the camera saw it -- or None: everything restyled.  For each frame size in
+        use it is cropped and resized ONCE on the host, as a frame of that size is, and every cached engine takes it on its own stream
+        ahead of its next launch (`Engine.set_masks`): no re-capture, and launches in flight keep the mask they were submitted with.
+        Through a worker (`VideoSDPipeline.remote(...).set_mask`) the call runs alone like every method but `infer`.  -> how many masks
+        this object has been given."""
+        if not self.keep_mask:
+            raise ValueError("set_mask needs a pipeline built with keep_mask=True")
+        self._mask_img = None if mask is None else self._mask_image(mask)
+        self._mask_sized = {}
+        self._mask_epoch += 1
+        return self._mask_epoch
+
+    def _launch_masks(self, masks, n: int, width: int, height: int):
+        """-> what `_install` gives the engine: None without `keep_mask`; one u8 [h][w] array per frame for `masks=[...]`; else the
+        (epoch, array or None) of `set_mask` at this frame size (sized once per size and mask)"""
+        if masks is not None:
+            if not self.keep_mask:
+                raise ValueError("masks= (one keep mask per frame) needs a pipeline built with keep_mask=True")
+            masks = list(masks)
+            if len(masks) != n:
+                raise ValueError(f"masks must hold one mask per frame: {len(masks)} mask(s) for {n} frame(s)")
+            return [np.full((height - height % 8, width - width % 8), 255, np.uint8) if m is None else self._size_mask(self._mask_image(m), width, height)
+                    for m in masks]
+        if not self.keep_mask:
+            return None
+        if self._mask_img is None:
+            return (self._mask_epoch, None)
+        if (width, height) not in self._mask_sized:
+            self._mask_sized[(width, height)] = self._size_mask(self._mask_img, width, height)
+        return (self._mask_epoch, self._mask_sized[(width, height)])
+
     color_amount = property(lambda self: self._color_a / COLOR_MAX_AMOUNT, doc="the colour-match amount in [0, 1], as the contract rounds it")
 
     # ------------------------------------------------------------------ LoRA adapters (include/vsd.h THE ADAPTER FUSE)
@@ -524,7 +593,7 @@ class VideoSDPipeline:
                                 controlnet=controlnet, seed=seed, controlnet_scale=controlnet_scale)[0]
 
     def infer_batch(self, imgs, prompt=["pixar, cg"], height=360, width=640, strength=0.4, steps=20, guidance_scale=7.5,
-                    ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1, prompts=None):
+                    ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1, prompts=None, masks=None):
         """Several frames (of different sessions, or consecutive frames of one stream) with the SAME options through
         one batched launch: the result `infer` gives each frame, up to kernel rounding (frames are denoised independently), one pass over the
         weights for all of them.  Extension of the reference surface; `RemotePipeline(batch=B)` coalesces queued
@@ -532,8 +601,12 @@ class VideoSDPipeline:
         prompts (objects built with `frame_prompts=True`): one prompt per frame, each what `prompt` accepts; frame i is then what `infer`
         gives it with prompts[i].  None: `prompt` for every frame.
         strength / controlnet_scale (objects built with `frame_options=True`): a number, or a sequence of one per frame; all strengths of a
-        launch must give the same number of timesteps."""
+        launch must give the same number of timesteps.
+        masks (objects built with `keep_mask=True`): one keep mask per frame, each what `set_mask` accepts (None: that frame is restyled
+        whole), for this launch alone; None: the mask of `set_mask` for every frame."""
         extra = {} if prompts is None else {"prompts": prompts}
+        if masks is not None:
+            extra["masks"] = masks
         return self.collect_batch(self.submit_batch(imgs, prompt=prompt, height=height, width=width, strength=strength, steps=steps,
                                                     guidance_scale=guidance_scale, ref=ref, style_fidelity=style_fidelity,
                                                     controlnet=controlnet, seed=seed, controlnet_scale=controlnet_scale, **extra))
@@ -554,7 +627,7 @@ class VideoSDPipeline:
         return ready
 
     def submit_batch(self, imgs, lane: int = 0, prompt=["pixar, cg"], height=360, width=640, strength=0.4, steps=20,
-                     guidance_scale=7.5, ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1, prompts=None):
+                     guidance_scale=7.5, ref=False, style_fidelity=0.0, controlnet=False, seed=42, controlnet_scale=1, prompts=None, masks=None):
         """First half of `infer_batch`: crop / resize, upload, enqueue -- returns a handle for `collect_batch` without
         waiting for the GPU.  `lane` picks one of the prepared engines of that (options, batch size): two lanes keep two
         launches in flight while the host works on the frames around them (the worker loop of dispatch.py does that).  Six phases in this
@@ -563,6 +636,7 @@ class VideoSDPipeline:
             raise ValueError(f"lane {lane}: this pipeline was built for {self.max_lanes} launch lane(s) (kwarg `lanes`)")
         prompt, plist = self._launch_prompts(len(imgs), prompt, prompts, ref)
         t0 = time.perf_counter()
+        masks = self._launch_masks(masks, len(imgs), width, height)  # (at the size asked for: sized by the rule `_launch_frames` sizes frames by)
         imgs, raw, i420, yuv, height, width = self._launch_frames(imgs, width, height, ref)
         self._note("crop_resize", t0)
         if plist is not None:  # one cache entry per frame (the same object for equal prompts)
@@ -574,7 +648,7 @@ class VideoSDPipeline:
                                           dict(prompt=prompt, height=height, width=width, steps=steps, ref=ref, controlnet=controlnet))
         seeds = self._launch_seeds(seed, len(imgs))
         eng = self._engine_for(key, pairs[0], len(imgs), lane, prompt=pblock, prompt_text=prompt)
-        self._install(eng, key, pblock, pairs)
+        self._install(eng, key, pblock, pairs, masks)
         np.random.seed(seed if seeds is None else seeds[0] & 0xFFFFFFFF)  # kept for parity with videopipeline.py:112 (nothing downstream consumes it)
         t0 = time.perf_counter()
         self._enqueue(eng, lane, imgs, raw, i420, width, height, seeds)
@@ -696,7 +770,7 @@ class VideoSDPipeline:
             raise ValueError(f"seed must be an int or a sequence of {n} ints (one per frame)")
         return [int(v) for v in seeds]
 
-    def _install(self, eng, key: PlanKey, pblock, pairs):
+    def _install(self, eng, key: PlanKey, pblock, pairs, masks=None):
         """Phase 5, after `_engine_for`: this lane's launch reads ITS copy of the constants (the other lanes may run other prompts); a changed
         frame slot is rewritten on this lane's stream ahead of the program, so nobody waits."""
         eng.use_prompts(pblock) if isinstance(pblock, list) else eng.use_prompt(pblock)
@@ -704,6 +778,12 @@ class VideoSDPipeline:
             eng.use_options(pairs)
         if self.color_match is not None and set(eng.color_a) != {self._color_a}:  # (`set_color_match` since this engine's last launch)
             eng.set_color_amount(self.color_amount)
+        if isinstance(masks, list):  # `masks=[...]`: this launch's own; the next launch without them takes `set_mask`'s again
+            eng.set_masks(masks)
+            eng._mask_pipe_epoch = None
+        elif masks is not None and eng._mask_pipe_epoch != masks[0]:  # (`set_mask` since this engine's last launch, or a new engine)
+            eng.set_masks(masks[1])
+            eng._mask_pipe_epoch = masks[0]
         if key.use_ref and eng._ref_epoch != self._ref_epoch:
             rf = np.asarray(center_crop_resize(self._ref_img.convert("RGB"), key.width, key.height), dtype=np.uint8)
             eng.ops.upload(eng.ref_u8, torch.from_numpy(np.array(rf, copy=True)))  # (PIL's buffer is read-only)
@@ -848,6 +928,8 @@ class VideoSDPipeline:
             mode.update(edges=self.edges, canny_thresholds=self.canny_thresholds)
         if self.color_match is not None:  # (likewise)
             mode.update(color_match=self.color_match, color_amount=self.color_amount)
+        if self.keep_mask:  # (likewise; SDXL and reference-only programs are refused by `prepare`, by name)
+            mode.update(keep_mask=True)
         eng.prepare(plan_key.height, plan_key.width, plan_key.steps, strength, controlnet_scale=cn_scale, use_controlnet=plan_key.use_cn,
                     batch=batch, ref_mode=plan_key.use_ref, autotune=self.tuning_mode != "table", **mode)
         plan.engines[(batch, lane)] = eng
@@ -919,6 +1001,9 @@ class VideoSDPipeline:
         if self.color_match is not None:
             raise ValueError(f'export_plan: this pipeline was built with color_match="{self.color_match}"; its programs call vsd_color_match, which is '
                              'not a plan function: export from a pipeline built with color_match=None (the default)')
+        if self.keep_mask:
+            raise ValueError("export_plan: this pipeline was built with keep_mask=True; its programs call vsd_mask_latent, vsd_latent_keep and "
+                             "vsd_mask_blend, which are not plan functions: export from a pipeline built without it")
         if self._loras:
             raise ValueError("export_plan: this pipeline was built with loras=[...]; a plan file would freeze the weights at the scales of the "
                              "moment and the C library has no entry point that moves them: export from a pipeline built without adapters")
@@ -936,6 +1021,10 @@ class VideoSDPipeline:
         """Another prompt's constants as a file for vsd_plan_load_prompt (a loaded plan takes it without a new plan)."""
         from .plan import export_prompt
 
+        if self.keep_mask:
+            raise ValueError("export_prompt: this pipeline was built with keep_mask=True; its programs have no plan file a prompt file could "
+                             "belong to (vsd_mask_latent, vsd_latent_keep and vsd_mask_blend are not plan functions): export from a pipeline "
+                             "built without it")
         if self._loras:
             raise ValueError("export_prompt: this pipeline was built with loras=[...]; a prompt's constants depend on the adapted weights and a "
                              "plan file knows nothing of them: export from a pipeline built without adapters")
