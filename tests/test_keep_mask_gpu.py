@@ -285,7 +285,8 @@ def _cpu(t):
 def walk(eng, seeds=None):
     """Run `program_serial` call by call.  Around every keep-mask call: snapshot the operands, run the call, compare what it wrote with
     the host twin applied to the snapshot, to the bit (`dec_in` by the lcm_step route).  -> (calls checked by name, out_u8 ahead of the
-    first call behind postprocess_rgb, out_u8 at the end)"""
+    first call behind postprocess_rgb, out_u8 at the end).  Every call is checked on ITS OWN arguments: that they are the contract's (the
+    next timestep's row, the frame's draw 0, its own x0) is the frame-level claim of tests/test_stage_oracle_gpu.py."""
     ops, Bn = eng.ops, eng.batch
     seen, raw = {k: 0 for k in OURS}, None
     for fn, a, k in eng.program_serial.calls:

@@ -1,6 +1,8 @@
 """Keep masks without a GPU: the host twins vsd_mask_blend_host / vsd_mask_latent_host / vsd_latent_keep_host against the numpy
 restatement of THE KEEP MASK (include/vsd.h) to the bit on every case of tests/keep_mask_cases.py; what they refuse; header, binding
-and build list; the engine's wiring of `keep_mask=` on the op emulator (backed by the twins); the class's `set_mask` and a worker."""
+and build list; the engine's wiring of `keep_mask=` on the op emulator (backed by the twins); the class's `set_mask` and a worker.
+The wiring tests here say which buffers each recorded call is handed; that the FRAME is the contract's frame (the right timestep, draw and
+latents behind those pointers) is held per frame against the CPU oracle by tests/test_stage_oracle_host.py and tests/test_stage_oracle_gpu.py."""
 import ctypes as Ct
 import os
 import re
