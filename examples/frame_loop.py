@@ -8,6 +8,8 @@ server.py:104-143), one worker process per GPU, frames sharded round-robin, drop
   python examples/frame_loop.py --fade-to "a charcoal sketch" --fade-frames 60 ...  (a cross-fade between two prompts, written as 60 mixes)
   python examples/frame_loop.py --color-match histogram:0.8 ...   (every output frame keeps its camera frame's colours, matched on the device)
   python examples/frame_loop.py --keep-mask banner.png ...   (black in the image: kept as the camera saw it; white: restyled; blended on the device)
+  python examples/frame_loop.py --edge-blur 1.4 ...   (the edge op reads a Gaussian-blurred copy of each frame: calmer edges)
+  python examples/frame_loop.py --keep-mask banner.png --mask-feather 4 ...   (the mask's hard edge feathered on the device: no seam)
 
 Prints one JSON line: frames offered / processed / dropped, output frames per second, p50 / p95 submit->result latency.
 """
@@ -60,6 +62,10 @@ async def run(args):
         extra.update(color_match=mode, color_amount=float(amount) if amount else 1.0)
     if args.keep_mask:  # FILE -> the constructor's keep_mask=True; the image itself goes to every worker below (`set_mask`, any size)
         extra.update(keep_mask=True)
+    if args.edge_blur is not None:  # SIGMA -> the constructor's edge_blur (`set_edge_blur` moves it live)
+        extra.update(edge_blur=args.edge_blur)
+    if args.mask_feather is not None:  # SIGMA -> the constructor's mask_feather (needs --keep-mask; `set_mask_feather` moves it live)
+        extra.update(mask_feather=args.mask_feather)
     workers = [RemotePipeline(factory=args.factory, batch=args.batch, device=i, **cfg, **extra) for i in range(args.gpus)]
     opts = dict(prompt=args.prompt, height=args.height, width=args.width, strength=args.strength, steps=args.steps,
                 controlnet_scale=args.controlnet_scale, seed=23)
@@ -133,6 +139,10 @@ def main(argv=None):
                     help="histogram or meanstd, and an amount in [0, 1] (default 1): transfer each camera frame's colours onto its output frame")
     ap.add_argument("--keep-mask", dest="keep_mask", default="", metavar="FILE",
                     help="an image of any size, read as gray: 0 / black is kept as the camera saw it, 255 / white is restyled, values between blend")
+    ap.add_argument("--edge-blur", dest="edge_blur", type=float, default=None, metavar="SIGMA",
+                    help="sigma in [0, 10] of a Gaussian blur ahead of the edge op, on the device: the ControlNet's edges come from the calmed copy")
+    ap.add_argument("--mask-feather", dest="mask_feather", type=float, default=None, metavar="SIGMA",
+                    help="sigma in [0, 10] of a Gaussian blur over the keep mask, on the device (needs --keep-mask)")
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--strength", type=float, default=0.6)

@@ -670,6 +670,42 @@ int vsd_mask_latent_host(const void* mask_u8, int frames, int h, int w, float* w
 int vsd_latent_keep_host(const void* x0, const float* weights_f32, const float* noise_f32, const float* coef, int coef_stride, int hw, int batch,
                          void* lat, void* den);
 
+/* ---- A small Gaussian blur of 8-bit frames, on the device (csrc/blur.hip, csrc/blur_core.h) -----------------------------------------
+ * The step the two stages above stop short of: camera noise makes the one-pixel edges of vsd_canny_control appear and vanish from frame
+ * to frame (every OpenCV recipe blurs ahead of Canny), and a hard-edged keep mask shows its seam (every inpainting UI has a "mask blur").
+ * Both are this one primitive, inside the recorded program.  The reference has no such stage; here it is opt-in and the default program
+ * does not change.
+ * THE BLUR CONTRACT (fixed; integers only; the device kernel, the host twin and the tests are held to it byte for byte):
+ *   operands    src and dst: packed u8 [frames][h][w][C], C = 1 or 3, any byte alignment; frame f at base + f*C*h*w, so frame bases fall
+ *               on any byte offset.  src and dst do not overlap (refused); src is only read.  Sides 1..VSD_RESAMPLE_MAX_SIDE, frames
+ *               1..1024.
+ *   tap table   int32 [34] = {R, w_0, w_1, ..., w_32}: radius 1 <= R <= VSD_BLUR_MAX_RADIUS; every w_i >= 0; w_i = 0 for i > R;
+ *               w_0 + 2*(w_1 + ... + w_R) == VSD_BLUR_ONE (16384) exactly.  Nothing else is asked of the taps (they need not be
+ *               monotone): the table is an operand, the contract says what taps do, not how they were made from a sigma, and no libm
+ *               result enters a kernel.
+ *   horizontal  per row y, column x, channel c:  H = sum over i = -R..R of w_|i| * src[y][clamp(x + i, 0, w - 1)][c]  -- the border is
+ *               replicated, the clamp is on the PIXEL index.  h16 = (H + 32) >> 6.  H <= 255 * 16384 = 4 177 920, so h16 is 0..65280:
+ *               the value times 256 (8 fractional bits), and it fits 16 bits.
+ *   vertical    V = sum over j = -R..R of w_|j| * h16[clamp(y + j, 0, h - 1)][x][c] <= 65280 * 16384 = 1 069 547 520.
+ *               dst[y][x][c] = (V + (1 << 21)) >> 22.  V + 2^21 < 2^31: 32-bit int arithmetic is exact throughout; dst <= 255.
+ *   It follows: the identity table {1, 16384, 0, ...} returns src byte for byte (h16 = 256 * src, V = 2^22 * src); a constant image
+ *   stays constant for every valid table (H = 16384 v, h16 = 256 v, V = 2^22 v), so an all-255 mask stays all-255 and an all-0 mask
+ *   all-0; every output byte is a function of the operands alone, so the result does not depend on how a kernel tiles the image or on
+ *   how the frames are split among calls.
+ * vsd_gauss_blur: taps_dev: the table in DEVICE memory, 4-byte aligned, read by the kernel when it runs (a captured graph holds the
+ *   pointer, not the values, as vsd_color_match does with amounts_dev).  ONE launch on `stream`, whatever the operands hold: no workspace,
+ *   no memset, no atomics, no host synchronisation; capturable.  The kernel clamps R into 1..32, so no table can make it index outside its
+ *   tile or the image: a table the host check would refuse gives unspecified bytes, never an out-of-range access.  A call of more than
+ *   2^23 tiles of 64 rows x 32 bytes (17 GB of frames) is refused: split it.
+ * vsd_gauss_blur_host: the contract as plain loops over HOST memory, taps on the host; no GPU and no context (VSD_ERR_ARG without a
+ *   message); it refuses an invalid table.
+ * Not a plan function: a program that records it has no plan-file export (VSD_VERSION and the plan format are unchanged). */
+#define VSD_BLUR_MAX_RADIUS 32
+#define VSD_BLUR_ONE 16384
+int vsd_gauss_blur(vsd_ctx* ctx, const void* src_u8, void* dst_u8, int frames, int h, int w, int channels,
+                   const void* taps_dev /* int32[34], DEVICE memory, read when the kernel runs */, void* stream);
+int vsd_gauss_blur_host(const void* src_u8, void* dst_u8, int frames, int h, int w, int channels, const int32_t* taps /* host */);
+
 /* ---- two independent operations as ONE grid per kernel ------------------------------------------------
  * The reference runs the ControlNet and then the UNet encoder of a denoising step -- the same topology with two weight sets on the
  * same latents (lcm_controlnet.py:539-577) -- as two sequences of cuDNN / cuBLAS launches.  Here the two walk in lock step:

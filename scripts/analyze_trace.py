@@ -6,7 +6,7 @@ trace, opsf = sys.argv[1], sys.argv[2]
 ops = json.load(open(opsf))
 ours = ("conv_gemm_kernel", "conv_gemm8_kernel", "conv_gemm_group_kernel", "conv_halo_kernel", "conv_c64", "tail_kernel", "adain_kernel", "splitk_reduce", "gn_stats", "gn_apply", "gn_fused", "layernorm_kernel", "attention_kernel", "attention_lazy", "attention_pair", "attention_lazy", "attention_pair",
         "preprocess_rgb", "sobel_max", "sobel_apply", "canny_tile", "canny_border", "canny_mark", "canny_write", "add_noise", "lcm_step", "postprocess",
-        "color_hist", "color_lut", "color_apply", "mask_blend", "mask_latent", "latent_keep")
+        "color_hist", "color_lut", "color_apply", "mask_blend", "mask_latent", "latent_keep", "gauss_blur")
 rows = [r for r in csv.DictReader(open(trace)) if any(o in r["Kernel_Name"] for o in ours)]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last eager frame = everything from the last preprocess_rgb kernel on

@@ -9,10 +9,10 @@ LIB = os.path.join(HERE, "libvsd.so")
 # the implicit-GEMM conv kernel is a template with ~60 instantiations: one translation unit per tile family, so that
 # the families compile in parallel (as one file the library took 4.5 minutes to build)
 SOURCES = ["api.hip", "plan.hip", "plan_options.hip", "conv_gemm.hip", "conv_t128x128.hip", "conv_t128x64.hip", "conv_t64x64.hip", "conv_t64x128.hip",
-           "conv_t256x128.hip", "conv_t256x256.hip", "conv_halo.hip", "conv_c64.hip", "fused_tail.hip", "norm.hip", "attention.hip", "elementwise.hip", "noise.hip", "prompt_fold.hip", "prompt_install.hip", "prompt_mix.hip", "frame_options.hip", "resample.hip", "yuv.hip", "canny.hip", "color_match.hip", "lora.hip", "keep_mask.hip"]
+           "conv_t256x128.hip", "conv_t256x256.hip", "conv_halo.hip", "conv_c64.hip", "fused_tail.hip", "norm.hip", "attention.hip", "elementwise.hip", "noise.hip", "prompt_fold.hip", "prompt_install.hip", "prompt_mix.hip", "frame_options.hip", "resample.hip", "yuv.hip", "canny.hip", "color_match.hip", "lora.hip", "keep_mask.hip", "blur.hip"]
 HEADERS = ["common.h", "conv_kernels.h", "conv_epilogue.inc", "conv_gemm_body.inc", "plan_dispatch.inc", "plan_options.h", os.path.join("..", "..", "include", "vsd.h")]
 OWN_HEADERS = {"canny.hip": ["canny_core.h"], "prompt_mix.hip": ["prompt_mix_core.h"], "color_match.hip": ["color_match_core.h"],
-               "lora.hip": ["lora_core.h", "prompt_mix_core.h"], "keep_mask.hip": ["keep_mask_core.h"]}  # headers only one source includes: a change there rebuilds that source alone
+               "lora.hip": ["lora_core.h", "prompt_mix_core.h"], "keep_mask.hip": ["keep_mask_core.h"], "blur.hip": ["blur_core.h"]}  # headers only one source includes: a change there rebuilds that source alone
 # attention keeps its O / S accumulators live across the key loop and touches them with VALU every tile (online-softmax
 # rescale, exp): with the default AGPR placement the compiler moves them through v_accvgpr_read/write every tile
 # (~190 of 1300 instructions in the d=40 kernel); VGPR-form MFMA operands remove those moves.

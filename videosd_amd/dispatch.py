@@ -745,6 +745,8 @@ class RemotePipeline:
         self.set_prompt_embeds = _RemoteMethod(self, "set_prompt_embeds")
         self.set_color_match = _RemoteMethod(self, "set_color_match")
         self.set_mask = _RemoteMethod(self, "set_mask")
+        self.set_edge_blur = _RemoteMethod(self, "set_edge_blur")
+        self.set_mask_feather = _RemoteMethod(self, "set_mask_feather")
         self.set_lora_scale = _RemoteMethod(self, "set_lora_scale")    # (runs alone like every method but `infer`: after the launches
         self.set_lora_scales = _RemoteMethod(self, "set_lora_scales")  # in flight have been collected; in a group every worker gets it)
         self.sync_prompt = _RemoteMethod(self, "__sync_prompt__")

@@ -25,6 +25,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import blur
 from . import lib as L
 from .blocks import (FRAME_OPTION_OPS, MAX_OPTION_ENTRIES, FramePromptLayout, FrameSlots, OptionEntry, OptionLayout,  # noqa: F401
                      PromptBlock, PromptLayout, PromptMix, controlnet_scales, mix_segments, option_segments, prompt_segments, same_source,
@@ -38,6 +39,33 @@ from .packing import _round_up as _ru
 from .program import SYNC_OPS, Arena, Recorder, capture, flat_calls, launches_by_kind
 
 KEEP_MASK_OPS = ("mask_latent", "latent_keep", "mask_blend")  # what `prepare(keep_mask=True)` records besides the default program's ops
+BLUR_SWITCHES = ("edge_blur", "mask_feather")  # the two uses of the device blur (include/vsd.h THE BLUR CONTRACT): `prepare` kwargs, keys of `Engine.taps`
+
+
+class TapBlock:
+    """One tap table of the device blur as an engine holds it: int32 [34] on the device, read by the recorded `gauss_blur` when it runs (a
+    captured graph holds the address), its pinned mirror, and the table the next launch runs with -- the pattern of the masks and the
+    colour amounts: a setter only notes, `sync` sends a changed table ahead of the program."""
+
+    def __init__(self, ops, sigma):
+        self.dev = ops.zeros(blur.TAPS, dtype=torch.int32)
+        self.host = torch.zeros(blur.TAPS, dtype=torch.int32, pin_memory=torch.cuda.is_available())
+        self.sigma, self.want, self.epoch, self.sent = None, None, 0, None
+        self.set(sigma)
+
+    def set(self, sigma):
+        taps = blur.gauss_taps(sigma)  # (refuses by name)
+        self.sigma = float(sigma)
+        if self.want is None or not np.array_equal(taps, self.want):
+            self.want = taps
+            self.epoch += 1
+
+    def sync(self, ops):
+        """136 bytes on the lane's stream, when the table changed (the lane's previous launch has been collected: nothing reads the mirror)"""
+        if self.sent != self.epoch:
+            self.host.numpy()[:] = self.want
+            ops.upload(self.dev, self.host)
+            self.sent = self.epoch
 
 
 def _env_switch(name: str, default: bool) -> bool:
@@ -210,6 +238,9 @@ class Engine:
         self._mask_epoch = 0         # ... counts the `set_masks` calls that changed `_mask_want`
         self._mask_sent = None       # ... and the epoch `mask_u8` holds (`_sync_mask`)
         self._mask_pipe_epoch = None  # ... and which mask of the pipeline `_mask_want` is (VideoSDPipeline sets it; None: a launch's own masks)
+        self.taps = {}               # the device blur's tap tables: "edge_blur" / "mask_feather" -> TapBlock, for the switches `prepare` was given
+        self.blur_u8 = None          # `edge_blur` with a ControlNet: the blurred frames, u8 [B][H][W][3]: what the edge ops read
+        self.mask_soft = None        # `mask_feather`: the feathered masks, u8 [B][H][W]: what `mask_latent` and `mask_blend` read
         self.ref_u8 = None           # `ref_mode`: the reference image
         self._ref_epoch = None       # ... and which reference image of the pipeline `ref_u8` holds (VideoSDPipeline sets it)
         self.noise = None            # the host draws on the device (None: `device_seed`)
@@ -1114,7 +1145,7 @@ class Engine:
                 use_controlnet: bool = True, use_graph: Optional[bool] = None, autotune: bool = True, batch: int = 1,
                 ref_mode: bool = False, device_seed: bool = False, frame_prompts: bool = False, frame_options: bool = False,
                 edges: str = "sobel", canny_thresholds=(100, 200), color_match: Optional[str] = None, color_amount=1.0,
-                keep_mask: bool = False):
+                keep_mask: bool = False, edge_blur=None, mask_feather=None):
         """Fix the frame geometry and schedule; build the static program and capture it into a hipGraph
         (the reference's intent at videopipeline.py:35-47, `compile_model`).
 
@@ -1167,7 +1198,17 @@ class Engine:
         give way to the input's), and `mask_blend(frame_u8 -> out_u8)` behind `postprocess_rgb` -- behind `color_match` when both are
         on: colours are matched over the whole frame first.  With all-255 masks the frames are the default program's bit for bit.  New
         masks are one B*H*W-byte copy ahead of the next launch (`_sync_mask`), no re-capture; a slot has masks of its own.  Composes with
-        device_seed, frame_prompts, frame_options, edges and color_match; not with ref_mode or an SDXL UNet.  No plan-file export."""
+        device_seed, frame_prompts, frame_options, edges and color_match; not with ref_mode or an SDXL UNet.  No plan-file export.
+
+        edge_blur / mask_feather: None (no buffer, no table, no launch: the program of before) or a sigma in [0, 10] of the device
+        Gaussian blur (THE BLUR CONTRACT of include/vsd.h; `videosd_amd.blur.gauss_taps`; 0: the identity table).  edge_blur: ONE
+        `gauss_blur` over all B frames ahead of the per-frame edge op, on its stream; `canny_control` / `sobel_control` read the blurred
+        copy (webcam noise no longer makes one-pixel edges flicker), `preprocess_rgb`, the encoder, `color_match` and `mask_blend` keep
+        reading the camera's frame.  Without a ControlNet (SDXL; use_controlnet=False) it is accepted and inert, as `edges` is.
+        mask_feather (needs keep_mask): ONE `gauss_blur` with C = 1 ahead of `mask_latent`; `mask_latent` and `mask_blend` read the soft
+        mask, `set_masks` keeps uploading the caller's own.  An all-255 mask stays all-255, so it still gives the default frames.
+        `set_edge_blur` / `set_mask_feather` change the sigma from the next launch on: 136 bytes ahead of the program, no re-capture.
+        No plan-file export (`vsd_gauss_blur` is not a plan function)."""
         edges, canny_thresholds = L.check_edges(edges, canny_thresholds)
         if edges == "canny" and not hasattr(self.ops, "canny_control"):
             raise ValueError('edges="canny" needs the op canny_control, which this ops object does not have')
@@ -1182,6 +1223,16 @@ class Engine:
                 raise ValueError(f"keep_mask=True needs the op(s) {', '.join(missing)}, which this ops object does not have")
             if ref_mode or self.unet.add_l1 is not None:
                 raise ValueError("keep_mask=True: reference-only (ref_mode) and SDXL programs have no keep-mask stages")
+        if mask_feather is not None and not keep_mask:
+            raise ValueError("mask_feather needs keep_mask=True: it feathers the keep masks, and this program has none")
+        sigmas = {k: v for k, v in (("edge_blur", edge_blur), ("mask_feather", mask_feather)) if v is not None}
+        for k, v in sigmas.items():
+            try:
+                blur.gauss_taps(v)
+            except ValueError as e:
+                raise ValueError(f"{k}: {e}") from None
+        if sigmas and not hasattr(self.ops, "gauss_blur"):
+            raise ValueError(f"{' / '.join(sigmas)} needs the op gauss_blur, which this ops object does not have")
         self._check_arguments(H, W, batch, use_controlnet, ref_mode, device_seed, frame_prompts, frame_options)
         sched = LCMSchedule(strength, steps)
         self._prepare_prompt_block(batch, frame_prompts)
@@ -1202,6 +1253,9 @@ class Engine:
             self.mask_w = self.ops.zeros(batch, (H // 8) * (W // 8), dtype=torch.float32)
             self._mask_host = torch.zeros(batch, H, W, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
             self.set_masks(None)
+        self.taps = {k: TapBlock(self.ops, v) for k, v in sigmas.items()}  # (this engine's own as well)
+        if "mask_feather" in self.taps:
+            self.mask_soft = self.ops.zeros(batch, H, W, dtype=torch.uint8)
         # The lock-step encoders are the one-stream form of EVERY program.  What a pair's grid looks like depends on the mode: a one-frame
         # program (latency mode) takes the pair's own table entry, timed alone; a coalesced launch on busy lanes (throughput mode) runs
         # the pair in the form its members have as launches of their own -- a latency-chosen form there occupies more workgroup-time
@@ -1218,7 +1272,7 @@ class Engine:
         self.plan = dict(H=H, W=W, steps=steps, strength=strength, cn_scale=controlnet_scale, cn=use_controlnet, n=len(sched), batch=batch,
                          ref_mode=bool(ref_mode), device_seed=bool(device_seed), frame_prompts=bool(frame_prompts), frame_options=bool(frame_options), tuned_for_lanes=bool(self.tune_for_lanes),
                          edge_mode=self.edges, canny_thresholds=self.canny_thresholds,  # ("edges" is taken: the event edges of the captured sequence)
-                         color_match=self.color_mode, keep_mask=self.keep_mask,
+                         color_match=self.color_mode, keep_mask=self.keep_mask, edge_blur="edge_blur" in self.taps, mask_feather="mask_feather" in self.taps,
                          sizes=self._level_sizes(H, W), timesteps=sched.timesteps, n_ops=len(self.program.calls), arena_bytes=self.arena.peak)
         self._warm_up_and_capture(autotune)
         return self.plan
@@ -1359,11 +1413,15 @@ class Engine:
             if side0:  # Sobel + the conditioning embedding only feed the ControlNet encoder (which runs on stream 1 too)
                 r.fork()
                 r.use_stream(1)
+            edge_src = frame_b
+            if "edge_blur" in self.taps:  # the edge ops alone read the calmed copy; everything else keeps the camera's frame
+                edge_src = self.blur_u8 = ops.zeros(B, H, W, 3, dtype=torch.uint8)
+                r.gauss_blur(frame_b, edge_src, B, H, W, 3, self.taps["edge_blur"].dev)
             for b in range(B):  # the edge map is normalised by ITS frame's maximum (canny_gpu.py:39)
                 if self.edges == "canny":
-                    r.canny_control(frame_b[b], H, W, *self.canny_thresholds, img(self.edge_u8, b, H * W), img(ctrl, b, H * W))
+                    r.canny_control(edge_src[b], H, W, *self.canny_thresholds, img(self.edge_u8, b, H * W), img(ctrl, b, H * W))
                 else:
-                    r.sobel_control(frame_b[b], H, W, 0.11, 0.8, img(self.edge_u8, b, H * W), img(ctrl, b, H * W))  # videopipeline.py:109
+                    r.sobel_control(edge_src[b], H, W, 0.11, 0.8, img(self.edge_u8, b, H * W), img(ctrl, b, H * W))  # videopipeline.py:109
             cond_emb = self._cond_embedding(r, ctrl, H, W)
             self.buffers["control"], self.buffers["cond_emb"] = ctrl, cond_emb
             if side0:
@@ -1380,8 +1438,12 @@ class Engine:
             self.buffers["ref_x0"] = ref_x0
         # every frame gets the same draws: the reference resets its RNG per frame
         sops.add_noise(r, x0, 0, 0, c[0:2], B, lat[0])
+        mask_read = self.mask_u8
+        if self.mask_soft is not None:  # the feathered masks: what both mask stages read from here on
+            r.gauss_blur(self.mask_u8, self.mask_soft, B, H, W, 1, self.taps["mask_feather"].dev)
+            mask_read = self.mask_soft
         if self.keep_mask:  # the latent weights of this launch's masks, ahead of the first step
-            r.mask_latent(self.mask_u8, B, H, W, self.mask_w)
+            r.mask_latent(mask_read, B, H, W, self.mask_w)
         mark = a.mark()
         for i in range(n):
             a.rewind(mark)
@@ -1439,7 +1501,7 @@ class Engine:
         if self.color_mode is not None:  # ahead of everything that reads `out_u8` (`collect_u8`, the queued `rgb_to_i420`)
             r.color_match(frame_b, out_b, B, H, W, self.color_mode, self.color_amounts)
         if self.keep_mask:  # (likewise ahead of every reader; the colours were matched over the whole frame first)
-            r.mask_blend(frame_b, out_b, self.mask_u8, B, H, W)
+            r.mask_blend(frame_b, out_b, mask_read, B, H, W)
         # program: what a lone launch runs (the ControlNet encoder on the side stream when `overlap_controlnet`);
         # program_serial: everything on the lane's own stream (the encoders in lock step when `twin_encoders`)
         self.program = r.flavor(0 if self.overlap_controlnet or not self._twin_now else 1)
@@ -1453,6 +1515,7 @@ class Engine:
         self._sync_options()
         self._sync_color()
         self._sync_mask()
+        self._sync_blur()
         if autotune:  # (only shapes missing from the shared table are timed: a slot with the parent's batch size finds all)
             self.autotune()
         self.program.run()
@@ -1584,6 +1647,29 @@ class Engine:
             self.ops.upload(self.mask_u8, self._mask_host)
             self._mask_sent = self._mask_epoch
 
+    def _set_blur(self, switch: str, sigma):
+        if switch not in self.taps:
+            raise ValueError(f"set_{switch} needs an engine prepared with {switch}=<sigma> (0 for none yet): this program has no such blur")
+        try:
+            self.taps[switch].set(sigma)
+        except ValueError as e:
+            raise ValueError(f"{switch}: {e}") from None
+
+    def set_edge_blur(self, sigma):
+        """The sigma of the blur ahead of the edge op, in [0, 10] (0: the identity table), for the launches from the next one on.  Only noted
+        here (a launch in flight keeps the table it was submitted with); `launch` sends a changed table ahead of the program: no
+        re-capture, no drain."""
+        self._set_blur("edge_blur", sigma)
+
+    def set_mask_feather(self, sigma):
+        """the same for the blur of the keep masks"""
+        self._set_blur("mask_feather", sigma)
+
+    def _sync_blur(self):
+        """changed tap tables of `set_edge_blur` / `set_mask_feather` on the lane's stream ahead of the program"""
+        for block in self.taps.values():
+            block.sync(self.ops)
+
     @staticmethod
     def host_noise(n_steps: int, h: int, w: int, ref: bool = False):
         """The CPU draws of one frame, in the reference's order: draw 0 = prepare_latents noise
@@ -1620,6 +1706,7 @@ class Engine:
         self._sync_options()
         self._sync_color()
         self._sync_mask()
+        self._sync_blur()
         if self.graph is not None:
             ov = self.overlap_launch if overlap is None else overlap
             self.ops.seq_launch(self.graph if ov else self.graph_serial)

@@ -745,6 +745,12 @@ class HipOps:
         self.ctx.call("vsd_color_match", self._p(src_u8), self._p(dst_u8), int(frames), int(h), int(w), int(L.COLOR_MODES[mode]),
                       self._p(amounts_dev), self._p(ws), self.s)
 
+    def gauss_blur(self, src, dst, frames, h, w, channels, taps_dev):
+        """`src` blurred into `dst` by THE BLUR CONTRACT of include/vsd.h (csrc/blur.hip): `frames` packed u8 [h][w][channels] frames each,
+        channels 1 or 3, any alignment, no overlap.  taps_dev: int32 [34] = {R, w_0 .. w_32} in device memory (`videosd_amd.blur`), read
+        when the kernel runs (a captured graph follows a later copy into it).  One launch, no workspace."""
+        self.ctx.call("vsd_gauss_blur", self._p(src), self._p(dst), int(frames), int(h), int(w), int(channels), self._p(taps_dev), self.s)
+
     def mask_blend(self, src_u8, dst_u8, mask_u8, frames, h, w):
         """`src_u8` blended into `dst_u8` in place by THE KEEP MASK of include/vsd.h (csrc/keep_mask.hip): `frames` packed [h][w][3] frames
         each, one u8 [h][w] mask per frame (255: dst stays, 0: the src pixel).  One launch, no workspace."""

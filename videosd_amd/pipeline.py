@@ -27,6 +27,8 @@ from . import config as C
 from . import checkpoints as CK
 from . import promptmix as PM
 from . import weights as W
+from .blur import gauss_taps
+from .engine import BLUR_SWITCHES
 from .frames import I420Frame, is_i420
 from .lcm import lcm_timesteps
 from .lib import COLOR_MAX_AMOUNT, RESAMPLE_MAX_SIDE, check_color_amount, check_color_match, check_edges
@@ -173,6 +175,15 @@ class VideoSDPipeline:
             frame.  Default False: no such stages, the same programs and bits as before.  Fixed for the life of the object; a new mask is
             one copy ahead of the next launch, no re-capture.  Composes with every switch above and with I420 frames; not with SDXL or
             reference-only frames (refused by name); such a pipeline has no `export_plan` / `export_prompt`.
+        edge_blur=SIGMA: a Gaussian blur of that sigma (0..10; THE BLUR CONTRACT of include/vsd.h, `videosd_amd.blur.gauss_taps`) ahead of the
+            edge op, inside the captured program: the ControlNet's edges are taken from a calmed copy of the frame, so sensor noise no
+            longer makes one-pixel `edges="canny"` lines appear and vanish from frame to frame (what OpenCV recipes do with `GaussianBlur`
+            ahead of `Canny`); the encoder, colour match and mask blend keep reading the camera's own frame.  Applies to either `edges`
+            mode; without a ControlNet tower (SDXL) it is accepted and inert.  Default None: no such stage, the same programs and bits.
+            `set_edge_blur(sigma)` changes it live (136 bytes ahead of an engine's next launch, no re-capture; 0: no blur).
+        mask_feather=SIGMA (needs keep_mask=True): the same blur over the keep masks ahead of both mask stages -- the "mask blur" slider of
+            inpainting UIs, so a hard-edged mask drawn or segmented on a client leaves no seam.  An all-255 mask stays all-255.
+            `set_mask_feather(sigma)` changes it live.  Neither switch has `export_plan` / `export_prompt`.
         lanes: launch lanes this instance may keep in flight (`submit_batch(lane=...)`, the worker loop of dispatch.py): lane l runs on launch
             stream l (ops.HipOps); with at most two lanes every lane also has a stream for its side branch.
         tuning_mode: "auto": shapes missing from the table are timed on this GPU at `prepare`; "table": never -- they take the deterministic
@@ -192,6 +203,9 @@ class VideoSDPipeline:
         self.color_match, self._color_a = check_color_match(kwargs.get("color_match"), kwargs.get("color_amount", 1.0))
         self.keep_mask = bool(kwargs.get("keep_mask", False))
         self._mask_img, self._mask_epoch, self._mask_sized = None, 0, {}  # `set_mask`: the mask as an "L" image, its count, (width, height) -> u8 [h][w]
+        self._blur = {k: self._check_sigma(k, kwargs[k]) for k in BLUR_SWITCHES if kwargs.get(k) is not None}  # switch -> sigma (`set_edge_blur`, `set_mask_feather`)
+        if "mask_feather" in self._blur and not self.keep_mask:
+            raise ValueError("mask_feather needs keep_mask=True: it feathers the keep masks, and this pipeline has none")
         self._loras = self._check_loras(kwargs.get("loras"))  # [(name, path, scale)]: loaded by `load_model`, fused on the device
         self.lora_skip_text_encoder = bool(kwargs.get("lora_skip_text_encoder", False))
         self._lora_scales, self.lora_text_encoder_keys_skipped = OrderedDict((n, s) for n, _p, s in self._loras), 0
@@ -442,6 +456,31 @@ class VideoSDPipeline:
         if (width, height) not in self._mask_sized:
             self._mask_sized[(width, height)] = self._size_mask(self._mask_img, width, height)
         return (self._mask_epoch, self._mask_sized[(width, height)])
+
+    @staticmethod
+    def _check_sigma(switch: str, sigma) -> float:
+        try:
+            gauss_taps(sigma)
+        except ValueError as e:
+            raise ValueError(f"{switch}: {e}") from None
+        return float(sigma)
+
+    def _set_blur(self, switch: str, sigma) -> float:
+        if switch not in self._blur:
+            raise ValueError(f"set_{switch} needs a pipeline built with {switch}=<sigma> (0 for none yet)")
+        self._blur[switch] = self._check_sigma(switch, sigma)
+        return self._blur[switch]
+
+    def set_edge_blur(self, sigma: float) -> float:
+        """The sigma, in [0, 10] (0: no blur), of the blur ahead of the edge op for every launch submitted from now on (`edge_blur=` of the
+        constructor switched the stage on).  Every cached engine takes the new tap table on its own stream ahead of its next launch
+        (`Engine.set_edge_blur`): no re-capture, and launches in flight keep the table they were submitted with.  Through a worker
+        (`VideoSDPipeline.remote(...).set_edge_blur`) the call runs alone like every method but `infer`.  -> the sigma."""
+        return self._set_blur("edge_blur", sigma)
+
+    def set_mask_feather(self, sigma: float) -> float:
+        """the same for the blur of the keep masks (`mask_feather=` of the constructor)"""
+        return self._set_blur("mask_feather", sigma)
 
     color_amount = property(lambda self: self._color_a / COLOR_MAX_AMOUNT, doc="the colour-match amount in [0, 1], as the contract rounds it")
 
@@ -778,6 +817,9 @@ class VideoSDPipeline:
             eng.use_options(pairs)
         if self.color_match is not None and set(eng.color_a) != {self._color_a}:  # (`set_color_match` since this engine's last launch)
             eng.set_color_amount(self.color_amount)
+        for switch, sigma in self._blur.items():  # (`set_edge_blur` / `set_mask_feather` since this engine's last launch)
+            if eng.taps[switch].sigma != sigma:
+                eng._set_blur(switch, sigma)
         if isinstance(masks, list):  # `masks=[...]`: this launch's own; the next launch without them takes `set_mask`'s again
             eng.set_masks(masks)
             eng._mask_pipe_epoch = None
@@ -930,6 +972,7 @@ class VideoSDPipeline:
             mode.update(color_match=self.color_match, color_amount=self.color_amount)
         if self.keep_mask:  # (likewise; SDXL and reference-only programs are refused by `prepare`, by name)
             mode.update(keep_mask=True)
+        mode.update(self._blur)  # (likewise: edge_blur / mask_feather, at the sigma of the moment)
         eng.prepare(plan_key.height, plan_key.width, plan_key.steps, strength, controlnet_scale=cn_scale, use_controlnet=plan_key.use_cn,
                     batch=batch, ref_mode=plan_key.use_ref, autotune=self.tuning_mode != "table", **mode)
         plan.engines[(batch, lane)] = eng
@@ -1001,6 +1044,9 @@ class VideoSDPipeline:
         if self.color_match is not None:
             raise ValueError(f'export_plan: this pipeline was built with color_match="{self.color_match}"; its programs call vsd_color_match, which is '
                              'not a plan function: export from a pipeline built with color_match=None (the default)')
+        if self._blur:
+            raise ValueError(f"export_plan: this pipeline was built with {' and '.join(self._blur)}; its programs call vsd_gauss_blur, which is not a "
+                             "plan function: export from a pipeline built without it")
         if self.keep_mask:
             raise ValueError("export_plan: this pipeline was built with keep_mask=True; its programs call vsd_mask_latent, vsd_latent_keep and "
                              "vsd_mask_blend, which are not plan functions: export from a pipeline built without it")
@@ -1021,6 +1067,9 @@ class VideoSDPipeline:
         """Another prompt's constants as a file for vsd_plan_load_prompt (a loaded plan takes it without a new plan)."""
         from .plan import export_prompt
 
+        if self._blur:
+            raise ValueError(f"export_prompt: this pipeline was built with {' and '.join(self._blur)}; its programs have no plan file a prompt file "
+                             "could belong to (vsd_gauss_blur is not a plan function): export from a pipeline built without it")
         if self.keep_mask:
             raise ValueError("export_prompt: this pipeline was built with keep_mask=True; its programs have no plan file a prompt file could "
                              "belong to (vsd_mask_latent, vsd_latent_keep and vsd_mask_blend are not plan functions): export from a pipeline "

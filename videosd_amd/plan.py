@@ -241,6 +241,10 @@ def export_plan(engine, path: str) -> dict:
     if engine.plan.get("color_match") is not None:
         raise ValueError(f'export_plan: this engine was prepared with color_match="{engine.plan["color_match"]}"; its program calls vsd_color_match, which is '
                          'not a plan function: export the plan of an engine prepared with color_match=None (the default)')
+    if engine.plan.get("edge_blur") or engine.plan.get("mask_feather"):
+        on = " and ".join(k for k in ("edge_blur", "mask_feather") if engine.plan.get(k))
+        raise ValueError(f"export_plan: this engine was prepared with {on}; its program calls vsd_gauss_blur, which is not a plan function: "
+                         "export the plan of an engine prepared without it")
     if engine.plan.get("keep_mask"):
         raise ValueError("export_plan: this engine was prepared with keep_mask=True; its program calls vsd_mask_latent, vsd_latent_keep and "
                          "vsd_mask_blend, which are not plan functions: export the plan of an engine prepared without it")
